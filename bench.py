@@ -2,14 +2,14 @@
 
 N = 1 (default): BASELINE configs[1] — synthetic 1024-sphere grid + checker plane, point light,
 1920x1080, AA=1 (scenes/c2_s1024.yaml).  One step = one frame rendered to the AA-averaged f64 image
-in HBM (Camera::render + canvas.rs box average, before `as u8`).  The line also carries the N = 1
-value of the multi-GPU workload (`scaling_anchor`), so the 1/2/4/8-GPU curve has its own anchor.
+in HBM (Camera::render + canvas.rs box average, before `as u8`).  With `--full` the line also carries the
+N = 1 value of the multi-GPU workload (`scaling_anchor`), so the 1/2/4/8-GPU curve has its own anchor.
 
 N > 1: BASELINE configs[2] — the same scene at 3840x2160 AA=3, reflective, depth 5 (C3), ONE frame
 per step split across the ranks in interleaved 8-row blocks (rank r renders output rows
 {y : (y // 8) % N == r}); each rank's f64 AA-averaged tile goes to rank 0 in one RCCL send (the
 library's group: one ncclSend per part, one ncclRecv per part into rank 0's staging buffer, one placement
-kernel per part), double-buffered so the transfer of frame k overlaps the render of frame k+1 ("scaling": "strong": the frame is fixed).  After the timed region
+kernel per part), double-buffered so the transfer of frame k overlaps the render of frame k+1 ("scaling": "strong": the frame is fixed).  With `--full`, after the timed region
 rank 0 checks that the gathered frame is bit-identical to its own single-part render.
 `--mode frames` (opt-in) is the render-farm sharding: one whole frame per rank per step, no
 data-path collective ("scaling": "weak").
@@ -19,9 +19,17 @@ torch.distributed.run child process, before anything touches the GPU); under tor
 WORLD_SIZE == N.  `--dry-run` runs the same multi-rank logic on CPU (gloo, the CPU oracle as the
 tile renderer at a thumbnail size): a rehearsal of the distributed path, never a measurement.
 
-Also reported: the dominant kernel's roofline (HIP events on the render stream over the timed
-region), and the CPU oracle (test-infrastructure restatement of the reference) timed on a bounded
-row sample on the host cores, whose rows are also compared with the GPU frame (max |d|).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+result line: nothing else.  `--dump-outputs DIR` also writes the frame the last timed step rendered to
+DIR/frame.npy (float64; the whole AA-averaged H x W x 3 image when it fits DUMP_LIMIT_BYTES, else a fixed
+seeded sample of its pixels), so two builds can be compared output for output: the scene files are the
+only input, so the same arguments render the same frame.
+
+`--full` adds everything else the benchmark measures or checks: the dominant kernel's roofline (HIP
+events on the render stream over a second pass of the K steps), the CPU oracle (test-infrastructure
+restatement of the reference) timed on a bounded row sample on the host cores, whose rows are also
+compared with the GPU frame (max |d|), the cold-frame measurements, the C3 scaling anchor, the serial
+comparison of `--in-flight`, and at N > 1 the tile-identity check and the single-GPU point.
 """
 import argparse
 import json
@@ -119,11 +127,19 @@ def main():
     ap.add_argument("--mode", choices=("frames", "tiles"), default=None,
                     help="multi-rank sharding: row tiles of one frame + RCCL transfer (default at N>1) or whole "
                          "frames per rank (opt-in render farm, weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: the kernel roofline (a second "
+                         "pass of the steps), the CPU baseline and its parity sample, cold frames, the C3 scaling "
+                         "anchor, the serial comparison of --in-flight, and at N>1 the tile identity and single-GPU "
+                         "point (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step rendered to DIR/frame.npy (float64; a fixed seeded "
+                         "pixel sample when the frame is larger than DUMP_LIMIT_BYTES)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity sample")
     ap.add_argument("--cpu-stride", type=int, default=None,
                     help="CPU sample: one 8-row band in every STRIDE bands (default sized to ~10-30 s)")
-    ap.add_argument("--no-anchor", action="store_true", help="N=1: skip the C3 scaling anchor")
-    ap.add_argument("--no-cold", action="store_true", help="N=1: skip the cold-frame measurements")
+    ap.add_argument("--no-anchor", action="store_true", help="--full at N=1: skip the C3 scaling anchor")
+    ap.add_argument("--no-cold", action="store_true", help="--full at N=1: skip the cold-frame measurements")
     ap.add_argument("--in-flight", type=int, default=1,
                     help="whole-frame steps: frames alternate over this many render contexts and streams (1 = "
                          "one frame at a time, the default: two measured no faster on C2 or C3, "
@@ -131,7 +147,7 @@ def main():
     ap.add_argument("--max-depth", type=int, default=None,
                     help="experiment: override the workload's recursion depth (the line then names it in config)")
     ap.add_argument("--kernel-events", choices=("separate", "timed"), default="separate",
-                    help="per-launch HIP events for the roofline: over a second pass of K steps (default) or "
+                    help="--full: per-launch HIP events for the roofline over a second pass of K steps (default) or "
                          "inside the timed region")
     ap.add_argument("--gather", choices=("abi", "torch"), default="abi",
                     help="tiles at N>1: the library's own RCCL group (rr_create_rank + rr_render_gather_device; the "
@@ -292,7 +308,27 @@ class Session:
             r.close()
 
 
-def timed_loop(sess, steps, warmup, distributed, dist, torch, kernel_events="separate"):
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: a whole C2-sized f64 frame (49.8 MB) fits; larger frames are sampled
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: DIR/frame.npy, the AA-averaged f64 frame of the last timed step.  A frame larger than
+    DUMP_LIMIT_BYTES is written as an (n, 3) array of its pixels at fixed, seeded, sorted flat indices (the same
+    indices for the same frame size in every run and build)."""
+    import numpy as np
+
+    out = np.ascontiguousarray(frame, dtype=np.float64)
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        px = out.reshape(-1, out.shape[-1])
+        n = DUMP_LIMIT_BYTES // (px.shape[1] * px.itemsize)
+        out = px[np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "frame.npy"), out)
+
+
+def timed_loop(sess, steps, warmup, distributed, dist, torch, kernel_events="separate", on_timed=None):
+    """kernel_events None: no per-launch HIP events at all (the plain run; kernel times come back empty).
+    on_timed: called right after the timed region has been synchronised, before any further pass."""
     def sync():
         if sess.pipe is not None:
             sess.pipe.drain()
@@ -314,12 +350,14 @@ def timed_loop(sess, steps, warmup, distributed, dist, torch, kernel_events="sep
     t_enq = time.perf_counter()
     sync()
     t1 = time.perf_counter()
-    if not in_region:
+    if on_timed is not None:
+        on_timed()
+    if kernel_events == "separate":
         sess.rend.kernel_profile(True)
         for _ in range(steps):
             sess.step()
         sync()
-    ktimes = sess.rend.kernel_times()
+    ktimes = sess.rend.kernel_times() if kernel_events else {}
     sess.rend.kernel_profile(False)
     stats = sess.rend.last_stats()
     elapsed = t1 - t0
@@ -537,18 +575,28 @@ def gpu_bench(args, world, mode, workload):
     big = WORKLOADS[workload][1] * WORKLOADS[workload][2] * WORKLOADS[workload][3] ** 2 > 20_000_000
     steps = args.steps if args.steps is not None else (10 if big else 50)
     warmup = args.warmup if args.warmup is not None else (2 if big else 10)
+    last = {}  # --dump-outputs: the frame of the last timed step, read back before any further pass renders
+
+    def keep_frame():
+        if rank == 0:
+            last["frame"] = sess.frame()
+
     elapsed, t_enq, ktimes, stats, in_region = timed_loop(sess, steps, warmup, distributed, dist, torch,
-                                                          args.kernel_events)
+                                                          args.kernel_events if args.full else None,
+                                                          keep_frame if args.dump_outputs else None)
+    if last.get("frame") is not None:
+        dump_outputs(args.dump_outputs, last.pop("frame"))
     samples_per_frame = sess.W * sess.H * sess.aa * sess.aa
     frames_per_step = world if not tiles else 1  # frames mode: every rank renders a whole frame per step
     value = frames_per_step * samples_per_frame * steps / elapsed / 1e6
-    roofline = roofline_of(sess, ktimes, stats, steps, in_region)
+    # per-launch kernel times need HIP events around every launch (a pass of their own by default): --full only
+    roofline = roofline_of(sess, ktimes, stats, steps, in_region) if args.full else None
 
     # tiles: the gathered frame must be bit-identical to one part rendering the whole frame (§8(e)); rank 0
     # also times that single-GPU render of the same workload (the other ranks wait at the barrier), so the
     # line carries its own 1-GPU point
     identity = single = None
-    if sess.multi:
+    if sess.multi and args.full:
         gathered = sess.frame() if rank == 0 else None
         if rank == 0:
             one = R.Renderer(local)  # a plain single-device context renders the whole frame as one part
@@ -567,16 +615,17 @@ def gpu_bench(args, world, mode, workload):
         dist.barrier()
 
     cpu = parity = anchor = cold = serial = None
-    if rank == 0 and world == 1 and not args.force_dist and sess.slots:
+    extras = args.full and rank == 0 and world == 1 and not args.force_dist  # the N = 1 legs of --full
+    if extras and sess.slots:
         # the same frames one at a time (one context, one stream): the per-frame latency a single render sees
         ser = Session(R, workload, dev, local, 0, 1, tiles, False, rend)
         s_el, _, s_kt, _, _ = timed_loop(ser, steps, warmup, False, dist, torch)
         serial = {"frames_in_flight": 1, "steps": steps, "ms_per_step": round(s_el / steps * 1e3, 4),
                   "value": round(samples_per_frame * steps / s_el / 1e6, 3),
                   "kernels_ms_per_step": {k: round(v[0] / steps, 4) for k, v in s_kt.items() if v[1]}}
-    if rank == 0 and world == 1 and not args.force_dist and not args.no_cold:
+    if extras and not args.no_cold:
         cold = [cold_frames(R, w, dev, local, torch) for w in dict.fromkeys([workload, "c4_teapot"])]
-    if rank == 0 and world == 1 and not args.force_dist:
+    if extras:
         if not args.no_cpu_baseline:
             cpu, parity = cpu_leg(sess, args, sess.frame())
         if not args.no_anchor and workload != MULTI_GPU_WORKLOAD:
@@ -612,8 +661,10 @@ def gpu_bench(args, world, mode, workload):
                 "tile_identity": identity, "scaling_anchor": anchor, "single_gpu": single,
                 "bands": sess.rend.bands() if sess.multi and args.gather == "abi" else None,
                 "speedup_vs_single_gpu": round(value / single["value"], 3) if single else None,
-                "kernels_ms_per_step": {k: round(v[0] / steps, 4) for k, v in ktimes.items() if v[1]},
+                "kernels_ms_per_step": {k: round(v[0] / steps, 4) for k, v in ktimes.items() if v[1]}
+                if args.full else None,
                 "host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 4),
+                "full": bool(args.full),
                 "stats_last_step": {k: stats[k] for k in ("rays", "shadow_rays", "shade_events", "n1n2_scans",
                                                           "prim_tests", "exact_flops", "wave_visits")}}
         print(json.dumps(line), flush=True)
@@ -667,12 +718,15 @@ def dry_run(args, world, mode, workload):
             render_tile(buf)
             pipe.submit(i)
         else:
-            render_tile(torch.zeros((len(rows), W, 3), dtype=torch.float64))
+            last = torch.zeros((len(rows), W, 3), dtype=torch.float64)
+            render_tile(last)
     if pipe is not None:
         pipe.drain()
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and steps > 0:
+        dump_outputs(args.dump_outputs, (pipe.frame if pipe is not None else last).numpy())
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

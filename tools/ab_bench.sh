@@ -4,6 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+BENCH_ARGS="--full ${BENCH_ARGS:---steps 20 --warmup 3}"  # the summary below reads the --full fields
 for spec in "$@"; do
   IFS='|' read -r label lib envs <<< "$spec"
   ( [ -n "$lib" ] && export RRAY_EXPERIMENT=1 RRAY_LIB=$PWD/$lib

@@ -15,7 +15,7 @@ IFS='|' read -r -a envs <<< "${ENVS:-}"
 for rep in ${REPS:-1 2}; do
   for wl in ${WLS:-c2_s1024}; do
     for e in "${envs[@]}"; do
-      env $e timeout -k 10 300 python bench.py --workload "$wl" --steps "${STEPS:-30}" --warmup 5 --no-cpu-baseline \
+      env $e timeout -k 10 300 python bench.py --workload "$wl" --full --steps "${STEPS:-30}" --warmup 5 --no-cpu-baseline \
         --no-anchor ${BENCH_ARGS:-} > gpurun_out/ab_run.log 2>&1 || { echo "bench failed: $wl [$e]"; tail -5 gpurun_out/ab_run.log; exit 1; }
       python - "$wl" "$e" <<'PY'
 import json, sys

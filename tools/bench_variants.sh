@@ -3,6 +3,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the summary below reads the roofline
 for v in ${VARIANTS:-default}; do
   case $v in
     default) env="RRAY_X=0";;

@@ -19,4 +19,4 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   rc=$?; [ $rc -gt 1 ] && exit $rc
 fi
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
-step bench 600 python bench.py --steps "$STEPS" --warmup 5 || exit 1
+step bench 600 python bench.py --full --steps "$STEPS" --warmup 5 || exit 1

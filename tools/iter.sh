@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 for wl in ${WLS:-c1_readme c2_s1024 c3_s1024_reflect c4_teapot c5_area_light}; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-anchor --workload $wl --steps ${STEPS:-20} --warmup ${WARM:-5} \
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-anchor --workload $wl --steps ${STEPS:-20} --warmup ${WARM:-5} \
     ${BENCH_ARGS:-} > gpurun_out/wl_$wl.log 2>&1 || { echo "$wl failed"; tail -5 gpurun_out/wl_$wl.log; exit 1; }
 done
 python tools/wl_summary.py

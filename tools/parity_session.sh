@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for wl in ${WLS:-c1_readme c4_teapot c5_area_light c3_s1024_reflect}; do
   echo "== $wl ($(date +%T))"
-  timeout -k 10 ${T:-600} python bench.py --workload "$wl" --steps ${STEPS:-5} --warmup 2 --no-anchor \
+  timeout -k 10 ${T:-600} python bench.py --workload "$wl" --full --steps ${STEPS:-5} --warmup 2 --no-anchor \
     > "gpurun_out/parity_$wl.log" 2>&1 || { echo "$wl failed rc=$?"; tail -5 "gpurun_out/parity_$wl.log"; exit 1; }
   python - "$wl" <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ mkdir -p gpurun_out/phase_times
 export RRAY_EXPERIMENT=1 RRAY_LIB=$PWD/abtest/phase/librray_amd.so
 for wl in ${WLS:-c4_teapot c2_s1024}; do
   for k in ${KS:-1 11 12 13 14 2 3 4 21 22 23 24 5 0}; do
-    RRAY_PHASE_EXIT=$k timeout -k 10 200 python bench.py --workload "$wl" --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
+    RRAY_PHASE_EXIT=$k timeout -k 10 200 python bench.py --workload "$wl" --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
       --no-anchor > gpurun_out/phase_times/${wl}_k$k.log 2>&1 || { echo "$wl k=$k failed"; tail -3 gpurun_out/phase_times/${wl}_k$k.log; exit 1; }
     python - "$wl" "$k" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for wl in c3_s1024_reflect c2_s1024; do
 done
 for wl in c3_s1024_reflect c2_s1024; do
   for f in 1 2; do
-    timeout -k 10 300 python bench.py --workload $wl --in-flight $f --no-cold --no-cpu-baseline --no-anchor \
+    timeout -k 10 300 python bench.py --full --workload $wl --in-flight $f --no-cold --no-cpu-baseline --no-anchor \
       > gpurun_out/pipe/b_${wl}_$f.log 2>&1 || { tail -5 gpurun_out/pipe/b_${wl}_$f.log; exit 1; }
     echo -n "in-flight $f "; python tools/wl_summary.py gpurun_out/pipe/b_${wl}_$f.log
   done

@@ -13,7 +13,7 @@ if [ "$TESTS" != none ]; then
   [ $rc -gt 1 ] && exit $rc
 fi
 for wl in ${WLS:-c2_s1024 c4_teapot}; do
-  timeout -k 10 300 python bench.py --workload "$wl" --steps "${STEPS:-20}" --warmup 3 --no-cpu-baseline --no-anchor \
+  timeout -k 10 300 python bench.py --workload "$wl" --full --steps "${STEPS:-20}" --warmup 3 --no-cpu-baseline --no-anchor \
     > "gpurun_out/quick_bench_$wl.log" 2>&1 || { echo "bench $wl failed"; tail -5 "gpurun_out/quick_bench_$wl.log"; exit 1; }
   python - "$wl" <<'PY'
 import json, sys

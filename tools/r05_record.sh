@@ -10,7 +10,7 @@ mkdir -p gpurun_out/parity
 for spec in "c3_s1024_reflect" "c4_teapot" "c5_area_light --cpu-stride 4"; do
   wl=${spec%% *}
   echo "== parity $spec ($(date +%T))"
-  timeout -k 10 600 python bench.py --workload $spec --steps 5 --warmup 2 --no-anchor \
+  timeout -k 10 600 python bench.py --full --workload $spec --steps 5 --warmup 2 --no-anchor \
     > "gpurun_out/parity/parity_$wl.log" 2>&1 || { echo "$wl failed"; tail -5 "gpurun_out/parity/parity_$wl.log"; exit 1; }
   grep -o '"parity_sample": {[^}]*}' "gpurun_out/parity/parity_$wl.log"
 done
