@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define RR_ABI_VERSION 10
+#define RR_ABI_VERSION 11
 
 /* error codes */
 #define RR_OK 0
@@ -274,6 +274,44 @@ int rr_last_stats(rr_ctx* ctx, rr_stats* stats);
 int rr_color_at(rr_ctx* ctx, int64_t n, const double* origins, const double* directions, int32_t remaining,
                 uint64_t seed, int32_t jitter_mode, double* out_rgb);
 int rr_is_shadowed(rr_ctx* ctx, int64_t n, const double* points, const double* light_positions, int32_t* out);
+
+/* ---- ABI 11: first-hit queries and depth / normal / object-id / albedo frames ----
+ * hit() + prepare_computations of one ray (scene.rs:128-136, intersection.rs:50-92): the first entry with t >= 0 of
+ * Scene::intersect's sorted list and the Computations the reference builds from it, every field bit for bit; n1 / n2
+ * are computed for every hit, as the reference does (not only for transparent materials). */
+typedef struct {
+    int32_t object;   /* rr_scene_desc id of the hit leaf (a CSG's or group's leaf, as Intersection.object); -1: no entry with t >= 0 */
+    int32_t inside;
+    double t, u, v;
+    double point[3], eyev[3], normalv[3], over_point[3], under_point[3], reflectv[3];
+    double n1, n2;
+} rr_hit;             /* 192 bytes; a miss has object -1 and every other field 0 */
+
+/* A batch of rays -> one rr_hit each.  Host buffers (origins / directions: n x 3 doubles), blocking; n == 0 is
+ * RR_OK.  Returns RR_E_NAN after writing `out` when a ray met a NaN t among >= 2 entries.  rr_last_stats then
+ * reports rays == samples == n, n1n2_scans == the number of hits, no shadow rays and no shading events.  A
+ * multi-device context answers on its first local device. */
+int rr_hit_at(rr_ctx* ctx, int64_t n, const double* origins, const double* directions, rr_hit* out);
+
+#define RR_AOV_DEPTH  1  /* double per sample: the hit's t (+inf: miss) */
+#define RR_AOV_NORMAL 2  /* 3 doubles: normalv (0,0,0: miss) */
+#define RR_AOV_OBJECT 4  /* int32: object id (-1: miss) */
+#define RR_AOV_ALBEDO 8  /* 3 doubles: material.pattern_at_object(object, over_point) as shade_hit reads it
+                            (material.rs:77-80; 0,0,0: miss) */
+/* The camera rays' first hits as image planes (arbitrary output values: a depth, normal, object-id or albedo pass
+ * for picking, compositing or a denoiser's guides).  `planes` ORs the RR_AOV_* wanted; each requested plane needs
+ * its buffer (NULL: RR_E_ARG), an unrequested plane's pointer is ignored.  Planes are per canvas SAMPLE —
+ * cam->vsize x cam->hsize, row-major, the layout of RR_OUT_CANVAS — and never averaged (ids and depths do not
+ * average); opts->aa only has to be consistent with the camera sizes, as in rr_render.  The rays are the colour
+ * frame's rays bit for bit.  Only part 0 of 1 without a band (else RR_E_ARG); max_depth, seed, jitter_mode and flags
+ * are ignored.  rr_render_aov: host buffers, blocking, RR_E_NAN after writing the planes when nan_rays > 0.
+ * rr_render_aov_device: device buffers on the context's device, enqueued on `hip_stream` (NULL: ctx stream) and
+ * NOT synchronised.  rr_last_stats after either: rays == samples, n1n2_scans == shadow_rays == shade_events == 0.
+ * A multi-device context renders the planes on its first local device. */
+int rr_render_aov(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, int32_t planes,
+                  double* depth, double* normal, int32_t* object, double* albedo, rr_stats* stats);
+int rr_render_aov_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, int32_t planes,
+                         void* d_depth, void* d_normal, void* d_object, void* d_albedo, void* hip_stream);
 
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for

@@ -79,8 +79,29 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_write_png", "rr_render_scene_from_file", "rr_render_scene_from_file_devices", "rr_create_multi",
            "rr_rccl_unique_id", "rr_create_rank", "rr_context_info", "rr_render_gather_device", "rr_create_virtual",
            "rr_unshuffle_host", "rr_stage_row_offset", "rr_build_digest", "rr_balance_bands", "rr_group_bands",
-           "rr_group_set_bands"]
+           "rr_group_set_bands", "rr_hit_at", "rr_render_aov", "rr_render_aov_device"]
 RCCL_ID_BYTES = 128
+
+# ABI 11: first-hit queries and AOV frames
+RR_AOV_DEPTH, RR_AOV_NORMAL, RR_AOV_OBJECT, RR_AOV_ALBEDO = 1, 2, 4, 8
+AOV_PLANES = {"depth": RR_AOV_DEPTH, "normal": RR_AOV_NORMAL, "object": RR_AOV_OBJECT, "albedo": RR_AOV_ALBEDO}
+
+
+class Hit(C.Structure):
+    """rr_hit: hit() + prepare_computations of one ray (192 bytes; a miss has object -1 and every other field 0)."""
+    _fields_ = [("object", C.c_int32), ("inside", C.c_int32), ("t", C.c_double), ("u", C.c_double), ("v", C.c_double),
+                ("point", C.c_double * 3), ("eyev", C.c_double * 3), ("normalv", C.c_double * 3),
+                ("over_point", C.c_double * 3), ("under_point", C.c_double * 3), ("reflectv", C.c_double * 3),
+                ("n1", C.c_double), ("n2", C.c_double)]
+
+
+def hit_dtype():
+    """The numpy structured dtype with rr_hit's layout (Renderer.hit_at returns an array of it)."""
+    import numpy as np
+
+    vec = {"point", "eyev", "normalv", "over_point", "under_point", "reflectv"}
+    return np.dtype([(n, np.int32 if t is C.c_int32 else np.float64, (3,) if n in vec else ()) for n, t in Hit._fields_],
+                    align=True)
 
 _lib = None
 
@@ -141,6 +162,11 @@ def lib():
     L.rr_balance_bands.argtypes = [_D, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int64)]
     L.rr_group_bands.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
     L.rr_group_set_bands.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32]
+    L.rr_hit_at.argtypes = [C.c_void_p, C.c_int64, _D, _D, C.POINTER(Hit)]
+    L.rr_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, _D, _D, _I, _D,
+                                C.POINTER(Stats)]
+    L.rr_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -34,7 +34,9 @@ UNIT_FLAGS = {u: ["-mllvm", "-disable-machine-licm"] for u in CHAIN_UNITS + TREE
 # the flat scenes' global-cull level kernels (C2's fused camera kernel): the scheduler's AMDGPU register-pressure
 # trackers measured C2 0.1176 -> 0.1166 ms; the same flag on every unit cost C3 and C4 1 % (profiles/r05/ab_trackers.txt)
 UNIT_FLAGS["render_levels_g0_gl.hip"] = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
-SOURCES = LEVEL_UNITS + CHAIN_UNITS + TREE_UNITS + ["render.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+# first-hit kernels (render_hit.inc hit_kernel: rr_hit_at, rr_render_aov); their walks are not cross-lane (XL off)
+HIT_UNITS = [f"render_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
+SOURCES = LEVEL_UNITS + CHAIN_UNITS + TREE_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 

@@ -74,6 +74,9 @@ struct rr_ctx {
     // workspace
     DBuf counters, lcount, hit, n12, n1n2, ev_a, ev_b, canvas, rays0, qout;
     DBuf deep, deep_count;  // chain kernels' deep queue (rr::DeepRec segments) and its segment counters
+    // first-hit queries (hit_kernel): node index -> rr_scene_desc object id (flatten's node_of_object inverted, built
+    // at upload), and rr_hit_at's result planes
+    DBuf node_object, hitrec, aov;  // aov: rr_render_aov's device planes
     // per-tile camera-ray bundles of the last camera / part layout (tile_bundle_kernel), reused while they match
     DBuf tiles;
     struct TileKey {
@@ -778,7 +781,7 @@ void rr_destroy(rr_ctx* c) {
     rr::trace("rr_destroy %p: free", (void*)c);
     for (DBuf* b : {&c->culls, &c->inner, &c->chunks, &c->nodes, &c->groups, &c->shapes, &c->tris, &c->mats, &c->pats, &c->lights, &c->textures, &c->texels, &c->counters,
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
-                    &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count})
+                    &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -820,6 +823,11 @@ int rr_scene_upload(rr_ctx* c, const rr_scene_desc* d) {
     HIPCHK(upload(c->lights, hs.lights, st));
     HIPCHK(upload(c->textures, hs.textures, st));
     HIPCHK(upload(c->texels, hs.texels, st));
+    std::vector<int32_t> node_object(hs.nodes.size(), -1);  // the ids hit_kernel reports (Intersection.object)
+    for (size_t i = 0; i < hs.node_of_object.size(); ++i)
+        if (hs.node_of_object[i] >= 0 && (size_t)hs.node_of_object[i] < node_object.size())
+            node_object[hs.node_of_object[i]] = (int32_t)i;
+    HIPCHK(upload(c->node_object, node_object, st));
     HIPCHK(hipStreamSynchronize(st));
     c->host = std::move(hs);
     // the level-0 tile order is the previous scene's tile costs: drop it (the next frame records new ones).
@@ -1219,6 +1227,184 @@ int rr_is_shadowed(rr_ctx* c, int64_t n, const double* points, const double* lig
     HIPCHK(claim.release());
     HIPCHK(hipStreamSynchronize(st));
     return RR_OK;
+}
+
+// ---- ABI 11: first-hit queries (render_hit.inc hit_kernel) ----
+static_assert(sizeof(rr_hit) == 192, "rr_hit is 192 bytes (rray.h)");
+
+int rr_hit_at(rr_ctx* c, int64_t n, const double* origins, const double* directions, rr_hit* out) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (c && c->group) return rr_hit_at(rr::group_local(c->group, 0), n, origins, directions, out);
+    if (!c || n < 0 || (n > 0 && (!origins || !directions || !out))) return fail(RR_E_ARG, "null argument");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    std::vector<double> rays((size_t)n * 6);
+    for (int64_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            rays[6 * i + k] = origins[3 * i + k];
+            rays[6 * i + 3 + k] = directions[3 * i + k];
+        }
+    HIPCHK(upload(c->rays0, rays, st));
+    // the records as planes: RR_HIT_DOUBLES double planes, then the two int planes
+    const size_t d_bytes = (size_t)n * rr::RR_HIT_DOUBLES * sizeof(double), i_bytes = (size_t)n * 2 * sizeof(int32_t);
+    HIPCHK(c->hitrec.ensure(d_bytes + i_bytes));
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.rec_d = c->hitrec.as<double>();
+    O.rec_i = reinterpret_cast<int32_t*>(c->hitrec.as<char>() + d_bytes);
+    O.stride = n;
+    rr::LevelArgs A{};
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.rays0 = c->rays0.as<double>();
+    A.nseg = A.nseg_out = 1;
+    A.counters = frame_counters(c, 2);
+    for (int64_t base = 0; base < n; base += c->batch) {
+        A.base = base;
+        A.n = std::min<int64_t>(c->batch, n - base);
+        set_level0_index(A);
+        HIPCHK(rr::launch_hit(c->S, A, O, st));
+    }
+    std::vector<double> hd((size_t)n * rr::RR_HIT_DOUBLES);
+    std::vector<int32_t> hi((size_t)n * 2);
+    HIPCHK(hipMemcpyAsync(hd.data(), O.rec_d, d_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hi.data(), O.rec_i, i_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_counters, frame_counters(c, 2), kCounterBytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(claim.release());
+    HIPCHK(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < n; ++i) {
+        rr_hit& h = out[i];
+        const auto f = [&](int k) { return hd[(size_t)k * n + i]; };
+        h.object = hi[i];
+        h.inside = hi[(size_t)n + i];
+        h.t = f(0);
+        h.u = f(1);
+        h.v = f(2);
+        for (int k = 0; k < 3; ++k) {
+            h.point[k] = f(3 + k);
+            h.eyev[k] = f(6 + k);
+            h.normalv[k] = f(9 + k);
+            h.over_point[k] = f(12 + k);
+            h.under_point[k] = f(15 + k);
+            h.reflectv[k] = f(18 + k);
+        }
+        h.n1 = f(21);
+        h.n2 = f(22);
+    }
+    // these are the context's last stats now (rr_last_stats): complete, nothing pending
+    collect_stats(c, &c->last);
+    c->last.samples = (uint64_t)n;
+    c->last.kernel_ms = 0.0;
+    c->stats_pending = false;
+    return c->last.nan_rays ? nan_fail(c->last.nan_rays) : RR_OK;
+}
+
+int rr_render_aov_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, int32_t planes, void* d_depth,
+                         void* d_normal, void* d_object, void* d_albedo, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (c && c->group)
+        return rr_render_aov_device(rr::group_local(c->group, 0), cam, o, planes, d_depth, d_normal, d_object, d_albedo,
+                                    hip_stream);
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    if (!cam || !o) return fail(RR_E_ARG, "null camera/options");
+    rr_render_opts opts = *o;
+    opts.max_depth = 0;  // ignored here (as seed, jitter_mode and flags): no recursion in a first-hit frame
+    int rc = check_opts(cam, &opts);
+    if (rc != RR_OK) return rc;
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "AOV frames are whole frames: part 0 of 1, no band");
+    const int32_t all = RR_AOV_DEPTH | RR_AOV_NORMAL | RR_AOV_OBJECT | RR_AOV_ALBEDO;
+    if (planes == 0 || (planes & ~all)) return fail(RR_E_ARG, "planes must be a non-empty combination of RR_AOV_*");
+    if (((planes & RR_AOV_DEPTH) && !d_depth) || ((planes & RR_AOV_NORMAL) && !d_normal) ||
+        ((planes & RR_AOV_OBJECT) && !d_object) || ((planes & RR_AOV_ALBEDO) && !d_albedo))
+        return fail(RR_E_ARG, "a requested plane has a null buffer");
+    const int64_t total = cam->hsize * cam->vsize;
+    if (total >= ((int64_t)1 << 31)) return fail(RR_E_LIMIT, "an AOV frame must hold fewer than 2^31 samples");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    rr::LevelArgs A{};
+    A.cam = dev_camera(cam);
+    A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
+                   A.cam.origin[3] == 1.0;
+    A.hs = cam->hsize;
+    A.lrows = cam->vsize;
+    A.aa = o->aa;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = o->block_rows > 0 ? o->block_rows : 8;
+    A.rays0 = nullptr;
+    A.nseg = A.nseg_out = 1;
+    rc = tile_bundles(c, A, st, &A.tile_bundles);  // the colour frames' cached table (same key: camera and layout)
+    if (rc != RR_OK) return rc;
+    A.base = 0;
+    A.level = 0;
+    A.n = total;
+    set_level0_index(A);
+    A.counters = frame_counters(c, 2);
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.depth = (planes & RR_AOV_DEPTH) ? static_cast<double*>(d_depth) : nullptr;
+    O.normal = (planes & RR_AOV_NORMAL) ? static_cast<double*>(d_normal) : nullptr;
+    O.object = (planes & RR_AOV_OBJECT) ? static_cast<int32_t*>(d_object) : nullptr;
+    O.albedo = (planes & RR_AOV_ALBEDO) ? static_cast<double*>(d_albedo) : nullptr;
+    HIPCHK(rr::launch_hit(c->S, A, O, st));
+    c->stats_src = frame_counters(c, 2);
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    c->stats_pending = true;
+    c->last.samples = (uint64_t)total;
+    return RR_OK;
+}
+
+int rr_render_aov(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, int32_t planes, double* depth,
+                  double* normal, int32_t* object, double* albedo, rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (c && c->group) return rr_render_aov(rr::group_local(c->group, 0), cam, o, planes, depth, normal, object, albedo, stats);
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    if (!cam || !o) return fail(RR_E_ARG, "null camera/options");
+    if (((planes & RR_AOV_DEPTH) && !depth) || ((planes & RR_AOV_NORMAL) && !normal) ||
+        ((planes & RR_AOV_OBJECT) && !object) || ((planes & RR_AOV_ALBEDO) && !albedo))
+        return fail(RR_E_ARG, "a requested plane has a null buffer");
+    if (cam->hsize <= 0 || cam->vsize <= 0 || cam->hsize > (1ll << 31) || cam->vsize > (1ll << 31))
+        return fail(RR_E_ARG, "bad camera size");
+    HIPCHK(hipSetDevice(c->device));
+    // the device planes back to back: depth, normal, albedo (doubles), then object
+    const size_t total = (size_t)cam->hsize * (size_t)cam->vsize;
+    const size_t off_normal = total * sizeof(double), off_albedo = off_normal + total * 3 * sizeof(double);
+    const size_t off_object = off_albedo + total * 3 * sizeof(double);
+    HIPCHK(c->aov.ensure(off_object + total * sizeof(int32_t)));
+    char* base = c->aov.as<char>();
+    int rc = rr_render_aov_device(c, cam, o, planes, base, base + off_normal, base + off_object, base + off_albedo, nullptr);
+    if (rc != RR_OK) return rc;
+    hipStream_t st = c->stream;
+    if (planes & RR_AOV_DEPTH) HIPCHK(hipMemcpyAsync(depth, base, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_NORMAL)
+        HIPCHK(hipMemcpyAsync(normal, base + off_normal, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_ALBEDO)
+        HIPCHK(hipMemcpyAsync(albedo, base + off_albedo, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_OBJECT)
+        HIPCHK(hipMemcpyAsync(object, base + off_object, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
 }
 
 }  // extern "C"

@@ -1882,6 +1882,7 @@ struct Comps {
     V3 point, eyev, normalv, over, under, reflectv;
     double n1, n2;
     bool own_ok;  // NF_OWN_SAFE node hit from outside: its shadow rays may skip it (own_node)
+    bool inside;  // Computations.inside (intersection.rs:57-60); read by hit_kernel only
 };
 
 // Intersection::prepare_computations (intersection.rs:50-60)
@@ -1933,6 +1934,7 @@ __device__ __forceinline__ void prepare(const DevScene& S, const Ray& r, const H
     }
     V3 nrm = normal_to_world(S, nd, ln);
     bool inside = dot3(nrm, c.eyev) < 0.0;
+    c.inside = inside;
     c.normalv = inside ? vneg(nrm) : nrm;
     c.over = vadd(c.point, vmul(c.normalv, RR_EPS));
     c.under = vsub(c.point, vmul(c.normalv, RR_EPS));

@@ -184,4 +184,26 @@ hipError_t launch_aa_f32(const double* canvas, float* out, int64_t width, int64_
 hipError_t launch_shadow_query(const DevScene& S, const double* pts, const double* lps, int64_t n, int32_t* out,
                                unsigned long long* counters, hipStream_t stream);
 
+// hit_kernel (render_hit.inc): hit() + prepare_computations of one ray per lane (scene.rs:128-136,
+// intersection.rs:50-92), no shading.  The rays are a level's level-0 rays: the camera's samples in 8x8 tiles
+// (A.rays0 == null: an AOV frame, rr_render_aov) or a caller's batch (A.rays0: rr_hit_at).  Not a KernelId: it is
+// timed by the frame's event pair only.
+struct HitOut {
+    const int32_t* node_object;  // node index -> rr_scene_desc object id (the context's table, built at upload)
+    // camera samples: the requested planes, row-major over the part's supersampled canvas (null: not requested)
+    double* depth;    // t, +inf on a miss
+    double* normal;   // 3 per sample: normalv
+    int32_t* object;  // object id, -1 on a miss
+    double* albedo;   // 3 per sample: material_color at over_point
+    // ray batches: the rr_hit fields as planes of `stride` entries each — ints {object, inside}, doubles {t, u, v,
+    // point, eyev, normalv, over_point, under_point, reflectv (3 each), n1, n2} (RR_HIT_DOUBLES planes)
+    int32_t* rec_i;
+    double* rec_d;
+    int64_t stride;
+};
+constexpr int RR_HIT_DOUBLES = 23;
+template <int G, bool LC>
+void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+hipError_t launch_hit(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+
 }  // namespace rr

@@ -397,6 +397,57 @@ class Renderer:
         check(lib().rr_color_at(self.h, len(o), _dp(o), _dp(d), remaining, seed, jitter_mode, _dp(out)))
         return out
 
+    def hit_at(self, origins, directions):
+        """Scene::intersect -> hit -> prepare_computations per ray (rr_hit_at): a structured array (_lib.hit_dtype():
+        object, inside, t, u, v, point, eyev, normalv, over_point, under_point, reflectv, n1, n2); a miss has
+        object -1 and zeros."""
+        o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float64).reshape(-1, 3)
+        out = np.zeros(len(o), _lib.hit_dtype())
+        check(lib().rr_hit_at(self.h, len(o), _dp(o), _dp(d), out.ctypes.data_as(C.POINTER(_lib.Hit))))
+        return out
+
+    @staticmethod
+    def _aov_mask(planes):
+        unknown = [p for p in planes if p not in _lib.AOV_PLANES]
+        if unknown:
+            raise ValueError(f"unknown AOV planes {unknown}: choose from {sorted(_lib.AOV_PLANES)}")
+        mask = 0
+        for p in planes:
+            mask |= _lib.AOV_PLANES[p]
+        return mask
+
+    def render_aov(self, cam, aa=1, planes=("depth", "normal", "object", "albedo"), part=0, nparts=1, band=None):
+        """The camera rays' first hits as planes per canvas sample (rr_render_aov): dict of depth (vsize, hsize) f64
+        (+inf: miss), normal (vsize, hsize, 3), object (vsize, hsize) int32 (-1: miss), albedo (vsize, hsize, 3), and
+        stats.  Never averaged: aa only has to divide the camera sizes.  Whole frames only (part / nparts / band are
+        passed through so that the library refuses them)."""
+        mask = self._aov_mask(planes)
+        o = _lib.RenderOpts(aa, 0, 0, 0, part, nparts, 8, 0, *(band or (0, 0)))
+        V, Hs = cam.vsize, cam.hsize
+        out = {"depth": np.zeros((V, Hs), np.float64) if "depth" in planes else None,
+               "normal": np.zeros((V, Hs, 3), np.float64) if "normal" in planes else None,
+               "object": np.zeros((V, Hs), np.int32) if "object" in planes else None,
+               "albedo": np.zeros((V, Hs, 3), np.float64) if "albedo" in planes else None}
+        st = _lib.Stats()
+        check(lib().rr_render_aov(self.h, C.byref(cam), C.byref(o), mask,
+                                  _dp(out["depth"]) if out["depth"] is not None else None,
+                                  _dp(out["normal"]) if out["normal"] is not None else None,
+                                  _ip(out["object"]) if out["object"] is not None else None,
+                                  _dp(out["albedo"]) if out["albedo"] is not None else None, C.byref(st)))
+        res = {k: v for k, v in out.items() if v is not None}
+        res["stats"] = st.as_dict()
+        return res
+
+    def render_aov_device(self, cam, opts, planes, d_depth=None, d_normal=None, d_object=None, d_albedo=None,
+                          stream=None):
+        """rr_render_aov_device: the planes into device buffers (ints: device pointers), ordered on `stream` (int or
+        None), not synchronised.  planes: names or an RR_AOV_* mask."""
+        mask = planes if isinstance(planes, int) else self._aov_mask(planes)
+        p = [C.c_void_p(x) if x else None for x in (d_depth, d_normal, d_object, d_albedo)]
+        check(lib().rr_render_aov_device(self.h, C.byref(cam), C.byref(opts), mask, *p,
+                                         C.c_void_p(stream) if stream else None))
+
     def is_shadowed(self, points, light_positions):
         p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         lp = np.ascontiguousarray(light_positions, np.float64).reshape(-1, 3)
