@@ -313,6 +313,36 @@ int rr_render_aov(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts,
 int rr_render_aov_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, int32_t planes,
                          void* d_depth, void* d_normal, void* d_object, void* d_albedo, void* hip_stream);
 
+/* ---- adaptive anti-aliasing (additive to ABI 11; test RR_HAS_ADAPTIVE) ----
+ * Supersamples only the pixels whose aa 1 colour differs from a neighbour's.  Inputs are rr_render's (a camera of
+ * W*aa x H*aa, opts->aa, max_depth, seed, jitter_mode) and a threshold:
+ *   1. probe   F1 = the aa 1 frame of the same view: what rr_render returns as out_avg for opts->aa = 1 and the camera
+ *              rr_camera_new(cam->hsize / aa, cam->vsize / aa, cam->field_of_view, cam->transform).  The library
+ *              derives that camera itself: cam's field_of_view and transform define it, not cam's pixel_size / half_*.
+ *   2. mask    pixel p is refined iff some pixel q of its 3x3 neighbourhood, clipped to the frame (q = p included),
+ *              has !(max_c |F1[p][c] - F1[q][c]| <= threshold) in plain f64.  So a NaN colour refines its
+ *              neighbourhood, threshold < 0 refines every pixel and +inf none (unless a colour is NaN).
+ *   3. refine  a refined pixel gets the pixel rr_render returns at opts->aa, bit for bit: the same aa*aa camera rays
+ *              with the full frame's area-light jitter identity, summed in canvas.rs:85-96 order and divided by
+ *              (double)(aa*aa).
+ *   4. result  out_avg = where(mask, that pixel, F1) (H*W*3 doubles); out_mask (H*W bytes, 0 / 1) and n_refined
+ *              are optional.  With aa == 1 the result is F1 and the mask is still the criterion's.
+ * RR_E_ARG: a null ctx / cam / opts / out_avg, a NaN threshold, part != 0, nparts != 1, a row band, any flag other
+ * than RR_NO_FRAME_TIMING, a multi-device or virtual context.  RR_E_LIMIT: (W*aa)*(H*aa) >= 2^32, or more samples
+ * than one pass of the context holds (2^27 unless RRAY_BATCH says otherwise).  Other errors are rr_render's;
+ * RR_E_NAN is returned after the outputs are written.  The RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN per-level
+ * paths do not serve the refine pass (RR_E_ARG).
+ * rr_last_stats / stats afterwards: samples = W*H + aa*aa*n_refined; the ray, shading and walk counters are the
+ * probe's plus the refine pass's; kernel_ms is one event pair around everything.
+ * rr_render_adaptive: host buffers, blocking.  rr_render_adaptive_device: device buffers on the context's device
+ * (d_avg doubles, d_mask bytes, d_n_refined one int64), everything enqueued on `hip_stream` (NULL: ctx stream) and
+ * NOT synchronised; no count visits the host between the passes. */
+#define RR_HAS_ADAPTIVE 1
+int rr_render_adaptive(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, double threshold,
+                       double* out_avg, uint8_t* out_mask, int64_t* n_refined, rr_stats* stats);
+int rr_render_adaptive_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, double threshold,
+                              void* d_avg, void* d_mask, void* d_n_refined, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

@@ -36,7 +36,14 @@ UNIT_FLAGS = {u: ["-mllvm", "-disable-machine-licm"] for u in CHAIN_UNITS + TREE
 UNIT_FLAGS["render_levels_g0_gl.hip"] = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
 # first-hit kernels (render_hit.inc hit_kernel: rr_hit_at, rr_render_aov); their walks are not cross-lane (XL off)
 HIT_UNITS = [f"render_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
-SOURCES = LEVEL_UNITS + CHAIN_UNITS + TREE_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+# adaptive frames' refine pass (render_adapt.hip): the level, chain and tree kernels compiled once more with the
+# listed-pixel level-0 source (RR_LISTED, namespace rr::listed), each built like the unit it mirrors
+LISTED_UNITS = [f"render_listed_{k}_g{g}_{lc}.hip" for k in ("chain", "tree", "levels") for g in (2, 1, 0) for lc in ("lds", "gl")]
+for _u in LISTED_UNITS:
+    _like = _u.replace("render_listed_", "render_")
+    if _like in UNIT_FLAGS:
+        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
+SOURCES = LEVEL_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 
@@ -134,7 +141,8 @@ def _resources(stderr):
 
 def cross_lane_kernel(demangled):
     """device_core.inc cross_lane_ok: kernels whose walks read other lanes' registers (v_readlane)."""
-    m = re.search(r"rr::(shade_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>", demangled)
+    m = re.search(r"rr::(?:listed::)?(shade_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
+                  demangled)
     if not m:
         return False
     args = [a.strip() for a in m.group(2).split(",")]

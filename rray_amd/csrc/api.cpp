@@ -77,6 +77,9 @@ struct rr_ctx {
     // first-hit queries (hit_kernel): node index -> rr_scene_desc object id (flatten's node_of_object inverted, built
     // at upload), and rr_hit_at's result planes
     DBuf node_object, hitrec, aov;  // aov: rr_render_aov's device planes
+    // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
+    // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
+    DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
     // per-tile camera-ray bundles of the last camera / part layout (tile_bundle_kernel), reused while they match
     DBuf tiles;
     struct TileKey {
@@ -115,6 +118,9 @@ struct rr_ctx {
     hipEvent_t aa_done = nullptr;
     rr_stats last{};
     bool stats_pending = false;
+    // the pending frame is an adaptive one: its refine pass's sample count is still on the device (adapt_counts[1]);
+    // rr_last_stats adds it to last.samples
+    bool adapt_pending = false;
     bool frame_timed = true;  // e0/e1 bracket the last frame
     // camera samples per wavefront pass: large, so that the deep levels of a frame (few, slow,
     // incoherent rays) run once per frame rather than once per batch; the queues of a 2^27-sample
@@ -373,6 +379,10 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
             if (!c->aa_stream) HIPCHK(hipStreamCreateWithFlags(&c->aa_stream, hipStreamNonBlocking));
         }
     }
+    // listed pixels (adaptive frames' refine pass): one batch, served by the in-wave kernels only
+    const bool listed = base_args.list != nullptr;
+    if (listed && (B < total || !(tree || chain || (fused && (k == 0 || max_depth == 0)))))
+        return fail(RR_E_ARG, "internal: the listed-pixel pass needs one batch of a production kernel family");
     const LevelPlan P = plan_levels(B, k, plan_depth, ext, fused);
     if (P.max_cap >= ((int64_t)1 << 31)) return fail(RR_E_LIMIT, "recursion queues exceed 2^31 events (lower max_depth)");
     if ((int)c->comb.size() < P.levels) {
@@ -397,7 +407,7 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
     // can send the chains still reflecting at depth RR_DEEP_FROM to a packed, segmented queue for a second launch.
     // Opt-in (RRAY_DEEP=1): on C3 the deep launch took 1.85 ms for what the camera waves did in 1.54 — the deep
     // rays' walks are latency-bound whether their waves are full or not
-    const bool spill = chain && !tree && aa_wave == 0 && !base_args.pw && max_depth >= rr::RR_DEEP_FROM && std::getenv("RRAY_DEEP") &&
+    const bool spill = chain && !tree && aa_wave == 0 && !base_args.pw && !base_args.list &&max_depth >= rr::RR_DEEP_FROM && std::getenv("RRAY_DEEP") &&
                        std::atoi(std::getenv("RRAY_DEEP")) == 1;
     const int64_t deep_seg_cap = (int64_t)256 << rr::RR_DEEP_SHIFT;
     const int64_t deep_nseg = (((B + 255) / 256) + (1 << rr::RR_DEEP_SHIFT) - 1) >> rr::RR_DEEP_SHIFT;
@@ -477,7 +487,7 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
             A.level = d;
             A.rem = max_depth - d;
             A.n = p.cap[d];
-            A.n_dev = d > 0 ? lc + (d - 1) * rr::LC_COUNT + rr::LC_CHILDREN : nullptr;
+            A.n_dev = d > 0 ? lc + (d - 1) * rr::LC_COUNT + rr::LC_CHILDREN : listed ? base_args.n_dev : nullptr;
             A.nseg = fused && d > 0 ? rr::RR_NSEG : 1;
             A.nseg_out = fused ? rr::RR_NSEG : 1;
             A.seg_cap = fused && d > 0 ? p.seg_cap[d] : 0;
@@ -524,7 +534,11 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
             }
             A.counters = frame_counters(c, c->epoch);
             A.counters_zero = (c->zero_next && d == 0 && base == 0) ? frame_counters(c, c->epoch ^ 1) : nullptr;
-            if (tree) {
+            if (listed) {
+                rr::KernelProf* kp = c->profile ? &c->prof : nullptr;
+                HIPCHK(tree ? rr::launch_tree_listed(c->S, A, st, kp)
+                            : chain ? rr::launch_chain_listed(c->S, A, st, kp) : rr::launch_level_listed(c->S, A, st, kp));
+            } else if (tree) {
                 HIPCHK(rr::launch_tree(c->S, A, st, c->profile ? &c->prof : nullptr));
             } else if (chain) {
                 if (spill) {  // camera launch appends to the deep queue's segments (level 1's counters)
@@ -781,7 +795,8 @@ void rr_destroy(rr_ctx* c) {
     rr::trace("rr_destroy %p: free", (void*)c);
     for (DBuf* b : {&c->culls, &c->inner, &c->chunks, &c->nodes, &c->groups, &c->shapes, &c->tris, &c->mats, &c->pats, &c->lights, &c->textures, &c->texels, &c->counters,
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
-                    &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov})
+                    &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
+                    &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -1076,6 +1091,7 @@ int rr_render_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, v
     c->stats_pending = true;
     // C_SAMPLES is not incremented by the wavefront kernels; it is the level-0 event count
     c->last.samples = (uint64_t)total;
+    c->adapt_pending = false;
     return RR_OK;
 }
 
@@ -1126,6 +1142,12 @@ int rr_last_stats(rr_ctx* c, rr_stats* s) {
     uint64_t samples = c->last.samples;
     int rc = finish_stats(c);
     if (rc != RR_OK) return rc;
+    if (c->adapt_pending) {  // an adaptive frame (finished by now): + the refine pass's samples, counted on the device
+        uint32_t events = 0;
+        HIPCHK(hipMemcpy(&events, c->adapt_counts.as<uint32_t>() + 1, sizeof events, hipMemcpyDeviceToHost));
+        samples += events;
+        c->adapt_pending = false;
+    }
     c->last.samples = samples;
     *s = c->last;
     return RR_OK;
@@ -1304,6 +1326,7 @@ int rr_hit_at(rr_ctx* c, int64_t n, const double* origins, const double* directi
     c->last.samples = (uint64_t)n;
     c->last.kernel_ms = 0.0;
     c->stats_pending = false;
+    c->adapt_pending = false;
     return c->last.nan_rays ? nan_fail(c->last.nan_rays) : RR_OK;
 }
 
@@ -1367,6 +1390,7 @@ int rr_render_aov_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* 
     HIPCHK(claim.release());
     c->stats_pending = true;
     c->last.samples = (uint64_t)total;
+    c->adapt_pending = false;
     return RR_OK;
 }
 
@@ -1400,6 +1424,149 @@ int rr_render_aov(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, int3
     if (planes & RR_AOV_OBJECT)
         HIPCHK(hipMemcpyAsync(object, base + off_object, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
+}
+
+// ---- adaptive anti-aliasing (render_adapt.hip) ----
+// what both entry points refuse before they look at the context (so a host without a device can test it)
+static int adaptive_check_args(const rr_camera* cam, const rr_render_opts* o, double threshold, const void* avg) {
+    if (!cam || !o || !avg) return fail(RR_E_ARG, "rr_render_adaptive: null camera / options / output image");
+    if (threshold != threshold) return fail(RR_E_ARG, "rr_render_adaptive: the threshold is NaN");
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "adaptive frames are whole frames: part 0 of 1, no band");
+    if (o->flags & ~RR_NO_FRAME_TIMING) return fail(RR_E_ARG, "adaptive frames take no flag but RR_NO_FRAME_TIMING");
+    return RR_OK;
+}
+
+int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, double threshold, void* d_avg,
+                              void* d_mask, void* d_n_refined, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = adaptive_check_args(cam, o, threshold, d_avg);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "adaptive frames need a single-device context (no multi-device or virtual context)");
+    rc = rr::render_validate(c, cam, o);  // rr_render's own checks (scene, depth, sizes)
+    if (rc != RR_OK) return rc;
+    const int32_t aa = o->aa;
+    const int64_t W = cam->hsize / aa, H = cam->vsize / aa;
+    if ((uint64_t)cam->hsize * (uint64_t)cam->vsize >= (1ull << 32))
+        return fail(RR_E_LIMIT, "an adaptive frame must hold fewer than 2^32 samples");
+    const int64_t total = W * H * aa * aa;  // the refine pass's capacity: every pixel listed
+    if (total > c->batch) return fail(RR_E_LIMIT, "an adaptive frame's samples must fit one pass of the context");
+    const bool tree = rr::tree_levels(c->S);
+    const bool in_wave = tree || rr::chain_levels(c->S, c->host.max_children, o->max_depth) ||
+                         (rr::fused_levels(c->S) && (c->host.max_children == 0 || o->max_depth == 0));
+    if (!in_wave)
+        return fail(RR_E_ARG, "adaptive frames are not served by the per-level paths (RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN)");
+    // 1. the probe's camera and options: the aa 1 frame of the same view
+    rr_camera cam1;
+    rc = rr_camera_new(W, H, cam->field_of_view, cam->transform, &cam1);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    const int64_t n_blocks = (W * H + rr::RR_ADAPT_BLOCK - 1) / rr::RR_ADAPT_BLOCK;
+    HIPCHK(c->adapt_flags.ensure((size_t)(W * H)));
+    HIPCHK(c->adapt_blocks.ensure((size_t)n_blocks * sizeof(uint32_t)));
+    HIPCHK(c->adapt_counts.ensure(2 * sizeof(uint32_t)));
+    HIPCHK(c->adapt_list.ensure((size_t)(W * H) * sizeof(uint32_t)));
+    if (aa > 1) HIPCHK(c->canvas.ensure((size_t)total * 3 * sizeof(double)));  // the refine pass's compact samples
+    c->frame_timed = !(o->flags & RR_NO_FRAME_TIMING);
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e0, st));
+    const int32_t block = o->block_rows > 0 ? o->block_rows : 8;
+    const auto camera_args = [&](const rr_camera* cm, int32_t a) {
+        rr::LevelArgs A{};
+        A.cam = dev_camera(cm);
+        A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
+                       A.cam.origin[3] == 1.0;
+        A.hs = cm->hsize;
+        A.aa = a;
+        A.part = 0;
+        A.nparts = 1;
+        A.block_rows = block;
+        A.rays0 = nullptr;
+        A.seed = o->seed;
+        A.jitter_mode = o->jitter_mode;
+        return A;
+    };
+    // the probe is rr_render_device's aa 1 frame, launch for launch: straight into d_avg; its first kernels zero the
+    // next frame's counters
+    rr::LevelArgs A1 = camera_args(&cam1, 1);
+    A1.lrows = H;
+    rc = tile_bundles(c, A1, st, &A1.tile_bundles);
+    if (rc != RR_OK) return rc;
+    c->zero_next = true;
+    rc = run_levels(c, A1, W * H, o->max_depth, nullptr, st, d_avg, 0, 0, nullptr);
+    c->zero_next = false;
+    if (rc != RR_OK) return rc;
+    // 2. mask, ordered compaction: the list and its length stay on the device
+    rr::AdaptArgs P{};
+    P.frame = static_cast<const double*>(d_avg);
+    P.avg = static_cast<double*>(d_avg);
+    P.w = W;
+    P.h = H;
+    P.aa = aa;
+    P.thr = threshold;
+    P.flags = c->adapt_flags.as<uint8_t>();
+    P.mask = static_cast<uint8_t*>(d_mask);
+    P.block_count = c->adapt_blocks.as<uint32_t>();
+    P.counts = c->adapt_counts.as<uint32_t>();
+    P.n_refined = static_cast<int64_t*>(d_n_refined);
+    P.list = c->adapt_list.as<uint32_t>();
+    P.samples = c->canvas.as<double>();
+    HIPCHK(rr::launch_adapt_select(P, st));
+    if (aa > 1) {
+        // 3. the refine pass: the listed pixels' samples through the scene's own kernel family, counted into the
+        // probe's counters (same epoch, nothing zeroed); launched for the capacity, the live count is P.counts[1]
+        rr::LevelArgs A2 = camera_args(cam, aa);
+        A2.lrows = 0;  // no tile layout: events are list entries
+        A2.list = P.list;
+        A2.list_w = (uint32_t)W;
+        A2.n_dev = P.counts + 1;
+        rc = run_levels(c, A2, total, o->max_depth, c->canvas.as<double>(), st);
+        if (rc != RR_OK) return rc;
+        // 4. canvas.rs:85-96 per listed pixel, over its aa 1 colour
+        HIPCHK(rr::launch_adapt_resolve(P, st));
+    }
+    c->stats_src = frame_counters(c, c->epoch);
+    c->epoch ^= 1;
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    c->stats_pending = true;
+    c->last.samples = (uint64_t)(W * H);  // + aa^2 x the refined pixels, still on the device: rr_last_stats adds them
+    c->adapt_pending = true;
+    return RR_OK;
+}
+
+int rr_render_adaptive(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, double threshold, double* out_avg,
+                       uint8_t* out_mask, int64_t* n_refined, rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = adaptive_check_args(cam, o, threshold, out_avg);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "adaptive frames need a single-device context (no multi-device or virtual context)");
+    rc = check_opts(cam, o);
+    if (rc != RR_OK) return rc;
+    const int64_t W = cam->hsize / o->aa, H = cam->vsize / o->aa;
+    HIPCHK(hipSetDevice(c->device));
+    // device outputs: the image in qout, then the count, then the mask
+    const size_t img = (size_t)(W * H) * 3 * sizeof(double);
+    HIPCHK(c->qout.ensure(img));
+    HIPCHK(c->adapt_mask.ensure((size_t)(W * H) + 16));
+    char* mbase = c->adapt_mask.as<char>();  // [0, 8): n_refined; [16, ...): the mask
+    rc = rr_render_adaptive_device(c, cam, o, threshold, c->qout.p, mbase + 16, mbase, nullptr);
+    if (rc != RR_OK) return rc;
+    int64_t n = 0;
+    HIPCHK(hipMemcpyAsync(out_avg, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
+    if (out_mask) HIPCHK(hipMemcpyAsync(out_mask, mbase + 16, (size_t)(W * H), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&n, mbase, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_refined) *n_refined = n;
     rr_stats local;
     rc = rr_last_stats(c, stats ? stats : &local);
     if (rc != RR_OK) return rc;

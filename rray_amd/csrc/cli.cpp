@@ -4,10 +4,13 @@
 // splits the frame over several GPUs of this host (rr_create_multi: row tiles + one RCCL transfer per part).
 // One option beyond the reference's: --aov <PREFIX> also writes <PREFIX>_normal.png (normalv * 0.5 + 0.5) and
 // <PREFIX>_albedo.png, the camera rays' first-hit planes (rr_render_aov) at the supersampled size.
+// --adaptive <THRESHOLD> renders the PNG through rr_render_adaptive: the aa 1 frame, supersampled (-a) only where a
+// pixel differs from a neighbour by more than THRESHOLD in some channel (one device).
 // No CPU fallback.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -25,6 +28,7 @@ static int usage(const char* msg) {
                  "  -o, --output <OUTPUT>  Name of the output file, default is output.png [default: output.png]\n"
                  "  -a, --aa <AA>          Anti-aliasing level (default 1) (max 5) [default: 1]\n"
                  "      --aov <PREFIX>     Also write <PREFIX>_normal.png and <PREFIX>_albedo.png (first-hit planes)\n"
+                 "      --adaptive <THRESHOLD>  Supersample only pixels that differ from a neighbour by more than THRESHOLD\n"
                  "  -h, --help             Print help\n  -V, --version          Print version\n");
     return 2;
 }
@@ -79,9 +83,54 @@ static int write_aov(const std::string& scene, long long width, long long height
     return rc;
 }
 
+// --adaptive: the colour image through rr_render_adaptive (camera.rs:113's depth 5, as the plain path)
+static int render_adaptive(const std::string& scene, long long width, long long height, int aa, int device,
+                           double threshold, const std::string& output) {
+    std::ifstream f(scene, std::ios::binary);
+    if (!f) {  // scene_builder_yaml.rs:434 panics "File does not exist"
+        std::fprintf(stderr, "rray: File does not exist (code %d)\n", RR_E_IO);
+        return RR_E_IO;
+    }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    rr_scene* S = nullptr;
+    rr_camera cam;
+    int rc = rr_scene_from_yaml(ss.str().c_str(), nullptr, width, height, aa, &S, &cam);
+    rr_ctx* ctx = nullptr;
+    if (rc == RR_OK) rc = rr_create(device, &ctx);
+    if (rc == RR_OK) rc = rr_scene_upload(ctx, rr_scene_desc_of(S));
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<double> avg(n * 3);
+    int64_t refined = 0;
+    if (rc == RR_OK) {
+        rr_render_opts o{};
+        o.aa = aa;
+        o.max_depth = 5;
+        o.nparts = 1;
+        o.block_rows = 8;
+        rc = rr_render_adaptive(ctx, &cam, &o, threshold, avg.data(), nullptr, &refined, nullptr);
+    }
+    if (rc == RR_OK) {
+        std::vector<uint8_t> rgba(n * 4);
+        rr_quantize(avg.data(), (int64_t)n, rgba.data());
+        rc = rr_write_png(output.c_str(), rgba.data(), width, height);
+        if (rc == RR_OK)
+            std::fprintf(stderr, "rray: adaptive: %lld of %lld pixels supersampled\n", (long long)refined, (long long)n);
+        else
+            std::fprintf(stderr, "rray: cannot write PNG (code %d)\n", rc);
+    } else {
+        std::fprintf(stderr, "rray: --adaptive: %s (code %d)\n", rr_last_error(), rc);
+    }
+    rr_destroy(ctx);
+    rr_scene_free(S);
+    return rc;
+}
+
 int main(int argc, char** argv) {
     long long width = 800, height = 600, aa = 1;
     std::string scene, output = "output.png", aov;
+    bool adaptive = false;
+    double threshold = 0.0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -104,6 +153,12 @@ int main(int argc, char** argv) {
         } else if (a == "--aov") {
             aov = val("--aov");
             if (aov.empty()) return usage("--aov needs a file name prefix");
+        } else if (a == "--adaptive") {
+            const char* v = val("--adaptive");
+            char* end = nullptr;
+            threshold = std::strtod(v, &end);
+            if (end == v || *end || std::isnan(threshold)) return usage("--adaptive needs a number (the colour threshold)");
+            adaptive = true;
         } else if (a == "-a" || a == "--aa") {
             if (!parse_usize(val("--aa"), aa)) return usage("must be a positive number");  // main.rs:21-27
             if (aa > 5) return usage("value must be less than or equal to 5");
@@ -136,11 +191,17 @@ int main(int argc, char** argv) {
     } else {
         devices.push_back(std::getenv("RRAY_DEVICE") ? std::atoi(std::getenv("RRAY_DEVICE")) : 0);
     }
-    int rc = rr_render_scene_from_file_devices(scene.c_str(), width, height, output.c_str(), (int)aa,
+    int rc;
+    if (adaptive) {
+        if (devices.size() != 1) return usage("--adaptive renders on one device");
+        if (render_adaptive(scene, width, height, (int)aa, devices[0], threshold, output) != RR_OK) return 1;
+    } else {
+        rc = rr_render_scene_from_file_devices(scene.c_str(), width, height, output.c_str(), (int)aa,
                                                (int)devices.size(), devices.data());
-    if (rc != RR_OK) {
-        std::fprintf(stderr, "rray: %s (code %d)\n", rr_last_error(), rc);
-        return 1;
+        if (rc != RR_OK) {
+            std::fprintf(stderr, "rray: %s (code %d)\n", rr_last_error(), rc);
+            return 1;
+        }
     }
     if (!aov.empty()) {
         rc = write_aov(scene, width, height, (int)aa, devices[0], aov);

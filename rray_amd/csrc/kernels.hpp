@@ -72,6 +72,12 @@ struct LevelArgs {
     int32_t jitter_mode;
     unsigned long long* counters;  // C_* totals
     unsigned long long* counters_zero;  // the next frame's counter buffer, zeroed by this frame's kernels (or null)
+    // listed pixels (adaptive frames' refine pass; the rr::listed kernels only, render_listed_*.hip): level-0 event i is
+    // sample i % aa^2 (dy outer, dx inner) of output pixel list[i / aa^2] (row-major index into the list_w-wide
+    // frame); n_dev holds the live event count (aa^2 x the listed pixels), the launch covers the capacity.  Last in
+    // the struct, so that no other field moves in the kernels that never read them.
+    const uint32_t* list;
+    uint32_t list_w;
 };
 
 struct CombArgs {
@@ -183,6 +189,46 @@ hipError_t launch_aa_f32(const double* canvas, float* out, int64_t width, int64_
                          KernelProf* prof = nullptr);
 hipError_t launch_shadow_query(const DevScene& S, const double* pts, const double* lps, int64_t n, int32_t* out,
                                unsigned long long* counters, hipStream_t stream);
+
+// Adaptive anti-aliasing (render_adapt.hip).  The refine pass renders the samples of a device-side
+// list of pixels (LevelArgs.list) with the level kernels compiled a second time, in namespace rr::listed with
+// RR_LISTED defined (render_listed_g<G>_<lds|gl>.hip): the production instantiations above do not carry the listed
+// source.  Every production dispatch is served: the fused level 0, the chain kernels and the tree kernels.
+namespace listed {
+template <int G, bool LC>
+void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
+template <int G, bool LC>
+void launch_chain_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof, bool deep);
+template <int G, bool LC>
+void launch_tree_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
+}  // namespace listed
+hipError_t launch_level_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+hipError_t launch_chain_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+hipError_t launch_tree_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+// The passes around it, all on the caller's stream with their counts in HBM:
+//   mask     rule: pixel p is refined iff some q of its clipped 3x3 neighbourhood has !(max_c |F[p][c] - F[q][c]| <= thr);
+//            writes flags (and mask, when not null) and one count per block of RR_ADAPT_BLOCK pixels
+//   scan     exclusive scan of the block counts (in place); n_list = refined pixels, n_events = n_list * aa^2,
+//            n_refined (int64, or null) = n_list
+//   scatter  list = the refined pixels' indices in ascending raster order (ballot + popcount inside the wave)
+//   resolve  per listed pixel: r = 0.0; r += sample (dy outer, dx inner); avg[p] = r / (double)(aa * aa)
+constexpr int RR_ADAPT_BLOCK = 256;
+struct AdaptArgs {
+    const double* frame;  // the aa 1 frame (3 doubles per pixel), overwritten at the listed pixels by resolve
+    int64_t w, h;
+    int32_t aa;
+    double thr;
+    uint8_t* flags;         // w * h
+    uint8_t* mask;          // the caller's, or null
+    uint32_t* block_count;  // ceil(w * h / RR_ADAPT_BLOCK): counts, then exclusive offsets
+    uint32_t* counts;       // [0] n_list, [1] n_events
+    int64_t* n_refined;     // the caller's, or null
+    uint32_t* list;         // w * h
+    const double* samples;  // the refine pass's colours: 3 doubles per level-0 event
+    double* avg;            // == frame
+};
+hipError_t launch_adapt_select(const AdaptArgs& P, hipStream_t stream);   // mask, scan, scatter
+hipError_t launch_adapt_resolve(const AdaptArgs& P, hipStream_t stream);
 
 // hit_kernel (render_hit.inc): hit() + prepare_computations of one ray per lane (scene.rs:128-136,
 // intersection.rs:50-92), no shading.  The rays are a level's level-0 rays: the camera's samples in 8x8 tiles

@@ -86,6 +86,25 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
         r.px = r.py = r.lrow = 0u;
         return r;
     }
+#ifdef RR_LISTED
+    // Listed pixels (the rr::listed kernels, adaptive frames' refine pass): event t is sample t % aa^2 (dy outer, dx
+    // inner: canvas.rs:85-96) of output pixel list[t / aa^2]; ls = t, the event's slot in the compact sample buffer.
+    // Whole frames only (part 0 of 1), so the canvas row is the sample row.  Events past the live count (A.n_dev)
+    // hold no sample (ok).
+    if (A.list) {
+        const uint32_t t = (uint32_t)(A.base + i);
+        const bool in = t < *A.n_dev;
+        if (ok) *ok = in;
+        const uint32_t aa = (uint32_t)A.aa, aa2 = aa * aa;
+        const uint32_t k = t / aa2, sm = t - k * aa2, dy = sm / aa, dx = sm - dy * aa;
+        const uint32_t p = in ? A.list[k] : 0u;
+        const uint32_t y = p / A.list_w, x = p - y * A.list_w;
+        r.ls = t;
+        r.px = x * aa + dx;
+        r.py = r.lrow = y * aa + dy;
+        return r;
+    }
+#endif
     const uint32_t hs = (uint32_t)A.hs;
     uint32_t lrow;
     if (PW && A.pw) {  // OWN indexing, one batch (base 0): the wave's slot, or the wave the cost order puts there

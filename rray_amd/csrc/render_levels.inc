@@ -766,7 +766,11 @@ __global__ void __launch_bounds__(256) RR_CHAIN_ATTR(PRE, G, AR) chain_kernel(De
     // camera launch: one lane per level-0 event; deep launch: block b walks chunks b / nseg, b / nseg + RR_DEEP_SPREAD,
     // ... of segment b % nseg of the deep queue
     const uint32_t seg = DEEP ? blockIdx.x % (uint32_t)A.nseg : 0u;
+#ifdef RR_LISTED  // listed pixels: launched for the capacity, the live count is on the device (blocks past it leave)
+    const int64_t n_live = DEEP ? (int64_t)A.seg_count[seg] : live_count(A);
+#else
     const int64_t n_live = DEEP ? (int64_t)A.seg_count[seg] : A.n;
+#endif
     const int64_t first = DEEP ? (int64_t)(blockIdx.x / (uint32_t)A.nseg) * RR_BLOCK : 0;
     if ((DEEP ? first : (int64_t)blockIdx.x * RR_BLOCK) >= n_live) return;
     if (!DEEP) zero_next_counters(A);
@@ -1079,9 +1083,11 @@ void launch_chain_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
     const size_t lds = cull_lds(S) + (pre ? (size_t)S.n_lights * 6 * 256 * sizeof(double) : 0) +
                        (S.has_area ? sizeof(AreaStage) : 0) + sizeof(ChainStage);
     Span s(prof, deep ? K_DEEP : K_CHAIN, st);
+#ifndef RR_LISTED  // listed pixels never leave their camera wave for the deep queue
     if (deep)
         launch_chain_deep<G, LC, true>(S, A, st, lds);
     else
+#endif
         launch_chain_deep<G, LC, false>(S, A, st, lds);
 }
 
@@ -1135,6 +1141,7 @@ void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
         launch_shade<G, LC, true>(S, A, st, pre, shade_lds);
         return;
     }
+#ifndef RR_LISTED  // the listed-pixel kernels serve the production dispatches only: no unfused level kernels
     {
         Span s(prof, K_TRACE, st);
         if (A.level > 0)
@@ -1153,5 +1160,6 @@ void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
         Span s(prof, K_SHADE, st);
         launch_shade<G, LC, false>(S, A, st, pre, shade_lds);
     }
+#endif
 }
 

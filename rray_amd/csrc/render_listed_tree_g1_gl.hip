@@ -1,0 +1,19 @@
+// render_listed_tree_g1_gl.hip — the color_at tree kernels with the listed-pixel source (adaptive frames' refine
+// pass, render_common.inc level0_px under RR_LISTED) for G = 1 (scenes with groups), culls read from global memory.  The same sources
+// as render_tree_g1_gl.hip and built like it, compiled into namespace rr::listed.
+#include <cstdlib>
+
+#include "device_core.inc"
+#include "kernels.hpp"
+#include "wavefront.hpp"
+
+#define RR_LISTED 1
+namespace rr {
+namespace listed {
+#include "render_common.inc"
+#include "render_levels.inc"
+#include "render_tree.inc"
+
+template void launch_tree_t<1, false>(const DevScene&, const LevelArgs&, hipStream_t, KernelProf*);
+}  // namespace listed
+}  // namespace rr

@@ -46,7 +46,11 @@ template <int G, bool LC, bool PRE, bool CP, bool AR, bool RM0, bool RMD>
 __global__ void __launch_bounds__(256) RR_TREE_ATTR(G, CP, AR) tree_kernel(DevScene S, LevelArgs A) {
     constexpr bool XL = false;
     if constexpr (!AR) load_prologue_args(A);
+#ifdef RR_LISTED  // listed pixels: launched for the capacity, the live count is on the device (blocks past it leave)
+    const int64_t n_live = live_count(A);
+#else
     const int64_t n_live = A.n;
+#endif
     if ((int64_t)blockIdx.x * RR_BLOCK >= n_live) return;
     zero_next_counters(A);
     if (LC) stage_culls(S);

@@ -448,12 +448,55 @@ class Renderer:
         check(lib().rr_render_aov_device(self.h, C.byref(cam), C.byref(opts), mask, *p,
                                          C.c_void_p(stream) if stream else None))
 
+    def render_adaptive(self, cam, aa, threshold, max_depth=5, seed=0, jitter_mode=0):
+        """rr_render_adaptive: the aa 1 frame of the view with the pixels adaptive_mask(that frame, threshold) marks
+        replaced by the pixels render(cam, aa) gives, bit for bit.  cam is the full camera (W*aa x H*aa; its
+        field_of_view and transform define the aa 1 probe camera).  -> dict(avg=(H, W, 3) f64, mask=(H, W) uint8,
+        n_refined, stats); stats['samples'] == W*H + aa*aa*n_refined."""
+        o = _lib.RenderOpts(aa, max_depth, seed, jitter_mode, 0, 1, 8, 0, 0, 0)
+        H, W = cam.vsize // max(aa, 1), cam.hsize // max(aa, 1)
+        avg = np.zeros((H, W, 3), np.float64)
+        mask = np.zeros((H, W), np.uint8)
+        n = C.c_int64(0)
+        st = _lib.Stats()
+        check(lib().rr_render_adaptive(self.h, C.byref(cam), C.byref(o), float(threshold), _dp(avg),
+                                       mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n), C.byref(st)))
+        return {"avg": avg, "mask": mask, "n_refined": int(n.value), "stats": st.as_dict()}
+
+    def render_adaptive_device(self, cam, opts, threshold, d_avg, d_mask=None, d_n_refined=None, stream=None):
+        """rr_render_adaptive_device: the same into device buffers (ints: device pointers; d_avg H*W*3 f64, d_mask H*W
+        bytes, d_n_refined one int64), ordered on `stream` (int or None), not synchronised."""
+        p = [C.c_void_p(x) if x else None for x in (d_avg, d_mask, d_n_refined, stream)]
+        check(lib().rr_render_adaptive_device(self.h, C.byref(cam), C.byref(opts), float(threshold), *p))
+
     def is_shadowed(self, points, light_positions):
         p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         lp = np.ascontiguousarray(light_positions, np.float64).reshape(-1, 3)
         out = np.zeros(len(p), np.int32)
         check(lib().rr_is_shadowed(self.h, len(p), _dp(p), _dp(lp), _ip(out)))
         return out.astype(bool)
+
+
+def adaptive_mask(frame, threshold):
+    """The adaptive frames' criterion in numpy (rray.h rr_render_adaptive, rule 2): pixel p of frame (H, W, 3) is
+    refined iff some q of its 3x3 neighbourhood, clipped to the frame (q = p included), has
+    !(max_c |frame[p][c] - frame[q][c]| <= threshold).  A NaN colour refines its neighbourhood; threshold < 0 refines
+    every pixel.  -> (H, W) bool.  A preview of what Renderer.render_adaptive will supersample, and its tests' reference."""
+    f = np.asarray(frame, np.float64)
+    if f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError(f"adaptive_mask: frame must have shape (H, W, 3); got {f.shape}")
+    if threshold != threshold:
+        raise ValueError("adaptive_mask: the threshold is NaN")
+    H, W = f.shape[:2]
+    out = np.zeros((H, W), bool)
+    with np.errstate(invalid="ignore"):  # inf - inf is NaN, which refines
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                ys, xs = slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx))
+                yq, xq = slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx))
+                d = np.max(np.abs(f[ys, xs] - f[yq, xq]), axis=2)  # np.max propagates NaN
+                out[ys, xs] |= ~(d <= threshold)
+    return out
 
 
 def quantize(avg):
