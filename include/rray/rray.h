@@ -266,6 +266,10 @@ int64_t rr_part_rows(int64_t height, int32_t part, int32_t nparts, int32_t block
  * every reflection chain in one chain kernel — deep only with RRAY_DEEP=1). */
 int rr_kernel_profile(rr_ctx* ctx, int enable);
 int rr_kernel_times(rr_ctx* ctx, double* ms, uint64_t* launches, int32_t n);
+/* How the last rr_render_device / rr_render_adaptive_device frame on this context launched its level-0 kernel
+ * (additive, ABI 11; no synchronisation): *blocks is the grid of the resident tile-loop launch and *heads the
+ * queue heads it used, both 0 when the frame ran the per-tile launch (or launched nothing).  Either may be NULL. */
+int rr_resident_launch(rr_ctx* ctx, int32_t* blocks, int32_t* heads);
 /* stats of the last rr_render/rr_render_device on this context (synchronises) */
 int rr_last_stats(rr_ctx* ctx, rr_stats* stats);
 

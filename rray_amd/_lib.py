@@ -80,7 +80,7 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_rccl_unique_id", "rr_create_rank", "rr_context_info", "rr_render_gather_device", "rr_create_virtual",
            "rr_unshuffle_host", "rr_stage_row_offset", "rr_build_digest", "rr_balance_bands", "rr_group_bands",
            "rr_group_set_bands", "rr_hit_at", "rr_render_aov", "rr_render_aov_device", "rr_render_adaptive",
-           "rr_render_adaptive_device"]
+           "rr_render_adaptive_device", "rr_resident_launch"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -135,6 +135,7 @@ def lib():
     L.rr_part_rows.restype = C.c_int64
     L.rr_kernel_profile.argtypes = [C.c_void_p, C.c_int]
     L.rr_kernel_times.argtypes = [C.c_void_p, _D, C.POINTER(C.c_uint64), C.c_int32]
+    L.rr_resident_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rr_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.rr_color_at.argtypes = [C.c_void_p, C.c_int64, _D, _D, C.c_int32, C.c_uint64, C.c_int32, _D]
     L.rr_is_shadowed.argtypes = [C.c_void_p, C.c_int64, _D, _D, _I]

@@ -34,6 +34,11 @@ UNIT_FLAGS = {u: ["-mllvm", "-disable-machine-licm"] for u in CHAIN_UNITS + TREE
 # the flat scenes' global-cull level kernels (C2's fused camera kernel): the scheduler's AMDGPU register-pressure
 # trackers measured C2 0.1176 -> 0.1166 ms; the same flag on every unit cost C3 and C4 1 % (profiles/r05/ab_trackers.txt)
 UNIT_FLAGS["render_levels_g0_gl.hip"] = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
+# the persistent level-0 loop (render_persist.inc persist_kernel: the C2 frame as one resident launch), built like the
+# unit whose kernel body it shares; its tile loop must not get loop-invariant constants hoisted into registers either
+# (with machine LICM the kernel spills 36 VGPRs at its 4 waves per SIMD; without, none: 125 VGPRs)
+PERSIST_UNITS = ["render_persist_g0_gl.hip"]
+UNIT_FLAGS["render_persist_g0_gl.hip"] = UNIT_FLAGS["render_levels_g0_gl.hip"] + ["-mllvm", "-disable-machine-licm"]
 # first-hit kernels (render_hit.inc hit_kernel: rr_hit_at, rr_render_aov); their walks are not cross-lane (XL off)
 HIT_UNITS = [f"render_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
 # adaptive frames' refine pass (render_adapt.hip): the level, chain and tree kernels compiled once more with the
@@ -43,7 +48,7 @@ for _u in LISTED_UNITS:
     _like = _u.replace("render_listed_", "render_")
     if _like in UNIT_FLAGS:
         UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-SOURCES = LEVEL_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 
@@ -141,7 +146,7 @@ def _resources(stderr):
 
 def cross_lane_kernel(demangled):
     """device_core.inc cross_lane_ok: kernels whose walks read other lanes' registers (v_readlane)."""
-    m = re.search(r"rr::(?:listed::)?(shade_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
+    m = re.search(r"rr::(?:listed::)?(shade_kernel|persist_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
                   demangled)
     if not m:
         return False
@@ -149,7 +154,7 @@ def cross_lane_kernel(demangled):
     g = int(args[0])
     if m.group(1) == "chain_kernel":  # <G, LC, PRE, CP, AR, RM0, RMD>: XL in the flat scenes' kernels only
         return g == 0 and args[3] == "false" and args[4] == "false"
-    if m.group(1) == "shade_kernel":  # <G, LC, FUSED, PRE, CP, RM, AR>
+    if m.group(1) in ("shade_kernel", "persist_kernel"):  # <G, LC, FUSED, PRE, CP, RM, AR>
         return g < 2 and args[4] == "false" and args[6] == "false"
     return g < 2
 

@@ -103,6 +103,11 @@ struct rr_ctx {
     // frame's first kernels zero the other buffer for the next frame
     int epoch = 0;
     bool zero_next = false;
+    bool next_zeroed = false;  // a launch of the running frame took the other buffer to zero (end_frame_counters)
+    // the persistent level-0 loop (rr::persist_plan): the blocks the GPU holds at once for the uploaded scene (< 0: not
+    // asked yet), and the last frame's launch (rr_resident_launch; blocks 0: per-tile)
+    int persist_resident = -1;
+    rr::PersistPlan persist_last{0, 0};
     unsigned long long* stats_src = nullptr;  // buffer holding the last frame's counters
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -226,6 +231,34 @@ constexpr int kRR_ORDER_EVERY = 64;  // frames between re-sorts of the level-0 t
 constexpr size_t kCounterBytes = (size_t)rr::RR_CNT_SLOTS * rr::RR_CNT_STRIDE * sizeof(unsigned long long);
 unsigned long long* frame_counters(rr_ctx* c, int k) {
     return c->counters.as<unsigned long long>() + (size_t)k * rr::RR_CNT_SLOTS * rr::RR_CNT_STRIDE;
+}
+
+// A frame's counter buffers.  begin: the frame's first run_levels counts into buffer `epoch` and has its first launch
+// clear the other one (zero_next).  end: the frame's buffer becomes the statistics' source, and the cleared one the
+// next frame's.  A frame that launched nothing (a part with no rows: total == 0) cleared nothing and counted nothing:
+// its buffer, still all zero, stays the next frame's — handed the other one, the next frame would count on top of the
+// counts of the frame before, and the persistent level-0 loop would find its queue heads (C_WORK) used up and render
+// no tile.
+void begin_frame_counters(rr_ctx* c) {
+    c->zero_next = true;
+    c->next_zeroed = false;
+    c->persist_last = {0, 0};
+}
+void end_frame_counters(rr_ctx* c) {
+    c->stats_src = frame_counters(c, c->epoch);
+    if (c->next_zeroed) c->epoch ^= 1;
+}
+
+// Heads of the persistent level-0 loop's tile queue (persist_map.hpp): a power of two <= RR_PERSIST_MAX_HEADS.
+// RRAY_PERSIST_HEADS=n overrides the default (rounded down to a power of two), read at launch.  128: C2 0.1087 ms
+// per frame against 0.1102 with 32 and 0.1086 with 256 (profiles/persist/ab_design.json, session 3).
+constexpr uint32_t kRR_PERSIST_HEADS = 128;
+uint32_t persist_heads() {
+    uint32_t want = kRR_PERSIST_HEADS;
+    if (const char* e = std::getenv("RRAY_PERSIST_HEADS")) want = (uint32_t)std::max(1, std::atoi(e));
+    uint32_t h = 1;
+    while (h * 2u <= want && h * 2u <= rr::RR_PERSIST_MAX_HEADS) h *= 2u;
+    return h;
 }
 
 // Worst-case queue bytes of a batch of nb level-0 events: every shading event queues max_children
@@ -534,6 +567,20 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
             }
             A.counters = frame_counters(c, c->epoch);
             A.counters_zero = (c->zero_next && d == 0 && base == 0) ? frame_counters(c, c->epoch ^ 1) : nullptr;
+            // a one-level, one-batch frame of full tiles may run as one resident launch (rr::persist_plan decides,
+            // below).  Its tile queue's heads are the C_WORK words of this frame's counter slots, which no kernel
+            // counts into: zero like the rest of the buffer — at rr_create, or by the first kernels of the frame
+            // before (counters_zero above).  A frame that launches nothing (a part with no rows) zeroes nothing, and
+            // does not take the buffer either: end_frame_counters leaves the untouched buffer to the next frame
+            rr::PersistPlan persist{0, 0};
+            if (fused && !chain && !tree && !listed && p.levels == 1 && B >= total && A.tile_fast && !A.pw &&
+                nb % 64 == 0 && nb / 64 < ((int64_t)1 << 31) && c->zero_next) {
+                A.persist_tiles = (uint32_t)(nb / 64);
+                A.persist_heads = persist_heads();
+                A.persist_head = A.counters + rr::C_WORK;
+                persist = rr::persist_plan(c->S, A, &c->persist_resident);
+            }
+            if (persist.blocks > 0) c->persist_last = persist;
             if (listed) {
                 rr::KernelProf* kp = c->profile ? &c->prof : nullptr;
                 HIPCHK(tree ? rr::launch_tree_listed(c->S, A, st, kp)
@@ -558,8 +605,12 @@ int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max
                     D.counters_zero = nullptr;
                     HIPCHK(rr::launch_chain(c->S, D, st, c->profile ? &c->prof : nullptr, true));
                 }
-            } else
+            } else if (persist.blocks > 0) {
+                HIPCHK(rr::launch_persist(c->S, A, persist, st, c->profile ? &c->prof : nullptr));
+            } else {
                 HIPCHK(rr::launch_level(c->S, A, st, c->profile ? &c->prof : nullptr));
+            }
+            if (A.counters_zero) c->next_zeroed = true;  // the launch above clears the next frame's buffer
             if (order_ok && d == 0 && (!c->order_valid || ++c->order_age >= kRR_ORDER_EVERY)) {
                 HIPCHK(rr::launch_tile_order(c->tile_cost.as<uint32_t>(), c->tile_perm.as<uint32_t>(),
                                              c->tile_hist.as<uint32_t>(), n_tiles, order_group, st));
@@ -850,6 +901,7 @@ int rr_scene_upload(rr_ctx* c, const rr_scene_desc* d) {
     c->order_valid = false;
     c->order_age = 0;
     c->tiles_valid = false;
+    c->persist_resident = -1;  // the resident launch's LDS follows the scene's lights
     rr::DevScene& S = c->S;
     S.culls = c->culls.as<rr::DevCull>();
     S.inner = c->inner.as<rr::DevCull>();
@@ -1078,14 +1130,13 @@ int rr_render_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, v
     const int32_t f32 = (o->flags & RR_OUT_AVG_F32) ? 1 : 0;
     rc = tile_bundles(c, A, st, &A.tile_bundles);
     if (rc != RR_OK) return rc;
-    c->zero_next = true;
+    begin_frame_counters(c);
     const AaPasses aap{d_avg, f32, W, o->aa};
     rc = run_levels(c, A, total, o->max_depth, canvas, st, direct_avg ? d_avg : nullptr, f32, wave_avg ? o->aa : 0,
                     (d_avg && !direct_avg) ? &aap : nullptr);
     c->zero_next = false;
     if (rc != RR_OK) return rc;
-    c->stats_src = frame_counters(c, c->epoch);
-    c->epoch ^= 1;
+    end_frame_counters(c);
     if (c->frame_timed) HIPCHK(hipEventRecord(c->e1, st));
     HIPCHK(claim.release());
     c->stats_pending = true;
@@ -1133,6 +1184,14 @@ int rr_kernel_times(rr_ctx* c, double* ms, uint64_t* launches, int32_t n) {
         if (launches) launches[k] = c->kcount[k];
     }
     return rr::K_COUNT;
+}
+
+int rr_resident_launch(rr_ctx* c, int32_t* blocks, int32_t* heads) {
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "multi-device context: ask a single-device context");
+    if (blocks) *blocks = c->persist_last.blocks;
+    if (heads) *heads = (int32_t)c->persist_last.heads;
+    return RR_OK;
 }
 
 int rr_last_stats(rr_ctx* c, rr_stats* s) {
@@ -1500,7 +1559,7 @@ int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_o
     A1.lrows = H;
     rc = tile_bundles(c, A1, st, &A1.tile_bundles);
     if (rc != RR_OK) return rc;
-    c->zero_next = true;
+    begin_frame_counters(c);
     rc = run_levels(c, A1, W * H, o->max_depth, nullptr, st, d_avg, 0, 0, nullptr);
     c->zero_next = false;
     if (rc != RR_OK) return rc;
@@ -1533,8 +1592,7 @@ int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_o
         // 4. canvas.rs:85-96 per listed pixel, over its aa 1 colour
         HIPCHK(rr::launch_adapt_resolve(P, st));
     }
-    c->stats_src = frame_counters(c, c->epoch);
-    c->epoch ^= 1;
+    end_frame_counters(c);
     if (c->frame_timed) HIPCHK(hipEventRecord(c->e1, st));
     HIPCHK(claim.release());
     c->stats_pending = true;

@@ -5,6 +5,7 @@
 #include <utility>
 #include <vector>
 
+#include "persist_map.hpp"
 #include "rr_device.hpp"
 #include "wavefront.hpp"
 
@@ -72,6 +73,12 @@ struct LevelArgs {
     int32_t jitter_mode;
     unsigned long long* counters;  // C_* totals
     unsigned long long* counters_zero;  // the next frame's counter buffer, zeroed by this frame's kernels (or null)
+    // persistent level-0 loop (render_persist.inc; persist_map.hpp): the frame's tiles (0: the frame does not
+    // qualify, per-tile launch), the number of queue heads (a power of two <= RR_CNT_SLOTS) and head 0 — head h is
+    // persist_head[h * RR_CNT_STRIDE], the C_WORK word of counter slot h of this frame's buffer, zero at the frame's start
+    uint32_t persist_tiles;
+    uint32_t persist_heads;
+    unsigned long long* persist_head;
     // listed pixels (adaptive frames' refine pass; the rr::listed kernels only, render_listed_*.hip): level-0 event i is
     // sample i % aa^2 (dy outer, dx inner) of output pixel list[i / aa^2] (row-major index into the list_w-wide
     // frame); n_dev holds the live event count (aa^2 x the listed pixels), the launch covers the capacity.  Last in
@@ -168,6 +175,21 @@ bool fused_levels(const DevScene& S);
 template <int G, bool LC>
 void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
 hipError_t launch_combine(const CombArgs& C, hipStream_t stream, KernelProf* prof = nullptr);
+// Level-0 fused frames of flat scenes as one resident launch (render_persist.inc persist_kernel): the grid covers the
+// GPU's resident capacity whatever the frame's size, and every wave loops over tiles it takes from the sharded queue
+// A.persist_head.  persist_plan: the launch that serves (S, A) that way, decided once per launch (blocks 0: the
+// per-tile launch_level) — A.persist_tiles set (api.cpp: one level, one batch, full tiles), a flat scene with global
+// culls, at most RR_PRELIT_LIGHTS point lights and no complex pattern (the one kernel instantiated), not
+// RRAY_NO_PERSIST=1, and at least as many tiles as resident wave slots unless RRAY_PERSIST_BLOCKS=n sets the grid.
+// *resident caches the blocks the GPU holds at once for this scene (the caller's, per context and scene; < 0: not
+// asked yet): the occupancy query runs once, and a launch costs two getenv reads on top of the per-tile one.
+struct PersistPlan {
+    int blocks;      // the grid; 0: per-tile launch
+    uint32_t heads;  // queue heads in use: A.persist_heads, and no more than the grid has waves
+};
+PersistPlan persist_plan(const DevScene& S, const LevelArgs& A, int* resident);
+hipError_t launch_persist(const DevScene& S, const LevelArgs& A, const PersistPlan& plan, hipStream_t stream,
+                          KernelProf* prof);
 // Fused scenes whose materials reflect: the whole reflection chain of every level-0 event inside its wave
 // (render_levels.inc chain_kernel), one launch per batch with no recursion queues
 bool chain_levels(const DevScene& S, int max_children, int max_depth);

@@ -67,8 +67,10 @@ __device__ __forceinline__ bool pixel_wave_sample(const LevelArgs& A, const Pixe
 // release their LDS together) or groups of four consecutive tiles (a block's waves: horizontally adjacent tiles, whose
 // output rows join into whole cache lines; A.tile_perm then maps the launch block to a tile group).  One-batch frames,
 // base 0.
+// tile >= 0: the caller's own tile (the persistent level-0 loop takes its tiles from a queue, queue_request below)
 template <bool ORDER = false>
-__device__ __forceinline__ uint32_t own_tile(const LevelArgs& A, int wave = -1) {
+__device__ __forceinline__ uint32_t own_tile(const LevelArgs& A, int wave = -1, int64_t tile = -1) {
+    if (tile >= 0) return (uint32_t)tile;
     const uint32_t w = wave >= 0 ? (uint32_t)wave : (uint32_t)uniform((int)threadIdx.x) >> 6;
     const uint32_t T0 = (uint32_t)(A.base >> 6) + blockIdx.x * 4u + w;
     if constexpr (ORDER) {
@@ -79,7 +81,8 @@ __device__ __forceinline__ uint32_t own_tile(const LevelArgs& A, int wave = -1) 
 }
 // PW: the kernel may run pixel waves (A.pw; the chain kernels); ok (PW) = the lane holds a sample
 template <bool OWN, bool ORDER = false, bool PW = false>
-__device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave = -1, bool* ok = nullptr) {
+__device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave = -1, bool* ok = nullptr,
+                                         int64_t tile = -1) {
     Px0 r;
     if (A.rays0) {
         r.ls = (uint32_t)(A.base + i);
@@ -108,7 +111,7 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
     const uint32_t hs = (uint32_t)A.hs;
     uint32_t lrow;
     if (PW && A.pw) {  // OWN indexing, one batch (base 0): the wave's slot, or the wave the cost order puts there
-        const PixelWave pw = pixel_wave(A, own_tile<ORDER>(A, wave));
+        const PixelWave pw = pixel_wave(A, own_tile<ORDER>(A, wave, tile));
         const bool in = pixel_wave_sample(A, pw, (uint32_t)lane_id(), r.px, lrow);
         if (ok) *ok = in;
         if (!in) r.px = lrow = 0u;
@@ -119,7 +122,7 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
     }
     if (A.tile_fast) {
         const uint32_t t = (uint32_t)(A.base + i);
-        const uint32_t T = OWN ? own_tile<ORDER>(A, wave) : ((ORDER && A.tile_perm) ? (A.order_group == 1 ? A.tile_perm[t >> 6] : A.tile_perm[t >> 8] * 4u + ((t >> 6) & 3u))
+        const uint32_t T = OWN ? own_tile<ORDER>(A, wave, tile) : ((ORDER && A.tile_perm) ? (A.order_group == 1 ? A.tile_perm[t >> 6] : A.tile_perm[t >> 8] * 4u + ((t >> 6) & 3u))
                                                                           : t >> 6);
         const uint32_t band = T / A.tiles_per_row;
         const uint32_t tc = T - band * A.tiles_per_row;
@@ -138,9 +141,9 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
     return r;
 }
 template <bool OWN, bool ORDER = false>
-__device__ __forceinline__ Px0 level0_px_if(const LevelArgs& A, int64_t i) {
+__device__ __forceinline__ Px0 level0_px_if(const LevelArgs& A, int64_t i, int64_t tile = -1) {
     if (A.level > 0) return {0u, 0u, 0u, 0u};
-    return level0_px<OWN, ORDER>(A, i);
+    return level0_px<OWN, ORDER>(A, i, -1, nullptr, tile);
 }
 
 // Camera::ray_for_pixel (camera.rs:75-93).  The camera inverse's 4th row is (0, 0, 0, 1) for every
@@ -175,9 +178,9 @@ __device__ __forceinline__ bool cam_tile(const LevelArgs& A) {
 
 // this wave's entry of the per-frame tile-bundle table (level 0, tile_fast, OWN indexing), or null
 template <bool ORDER = false>
-__device__ __forceinline__ const float* cam_bundle_of(const LevelArgs& A, int wave = -1) {
+__device__ __forceinline__ const float* cam_bundle_of(const LevelArgs& A, int wave = -1, int64_t tile = -1) {
     if (!A.tile_bundles || !cam_tile(A)) return nullptr;
-    return A.tile_bundles + (size_t)own_tile<ORDER>(A, wave) * RR_TILE_BUNDLE_FLOATS;
+    return A.tile_bundles + (size_t)own_tile<ORDER>(A, wave, tile) * RR_TILE_BUNDLE_FLOATS;
 }
 
 // the ray of event i at this level; q = level0_px(A, i) (used at level 0 only); camera rays also
@@ -261,6 +264,20 @@ __device__ __forceinline__ int32_t wave_append(unsigned int* ctr, bool want) {
     base = (unsigned int)__builtin_amdgcn_readlane((int)base, leader);
     const uint64_t below = lane == 0 ? 0ull : ((~0ull) >> (64 - lane));
     return want ? (int32_t)(base + (unsigned int)__popcll(m & below)) : -1;
+}
+
+// Sharded work queue (persist_map.hpp; the persistent level-0 loop, render_persist.inc): H heads, head h at
+// head[h * RR_CNT_STRIDE], each counting the tickets handed out.  Accesses to one head serialise memory-side (about
+// 11 ns each, loads included): a wave touches only its home head, once per tile.  queue_request takes the next ticket of head h for the
+// wave — one returning device atomic from lane 0 (a vector instruction); the ticket stays in lane 0's register until
+// queue_ticket broadcasts it, so the request can be issued ahead of the work that hides its latency.
+__device__ __forceinline__ uint32_t queue_request(unsigned long long* head, uint32_t h) {
+    uint32_t k = 0;
+    if (lane_id() == 0) k = (uint32_t)atomicAdd(head + (size_t)h * RR_CNT_STRIDE, 1ull);
+    return k;
+}
+__device__ __forceinline__ uint32_t queue_ticket(uint32_t requested) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)requested, 0);
 }
 
 // The live event count of a level.  Levels >= 1 are launched with their worst-case grid (the

@@ -385,6 +385,12 @@ class Renderer:
             check(k)
         return {_lib.KERNELS[i]: (ms[i], int(n[i])) for i in range(k)}
 
+    def resident_launch(self):
+        """(blocks, heads) of the last frame's resident tile-loop launch; (0, 0): it ran the per-tile launch."""
+        blocks, heads = C.c_int32(0), C.c_int32(0)
+        check(lib().rr_resident_launch(self.h, C.byref(blocks), C.byref(heads)))
+        return blocks.value, heads.value
+
     def last_stats(self):
         st = _lib.Stats()
         check(lib().rr_last_stats(self.h, C.byref(st)))

@@ -17,7 +17,8 @@ KEYS = ["VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occu
 
 
 def resources(src, defines):
-    cmd = [B.HIPCC] + B.COMMON + B.DEVICE + ["-D" + d for d in defines] + [
+    # built as build.py builds the unit (its per-unit flags decide spills: the persistent loop's unit, the C2 unit)
+    cmd = [B.HIPCC] + B.COMMON + B.DEVICE + B.UNIT_FLAGS.get(src, []) + ["-D" + d for d in defines] + [
         "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(B.CSRC, src), "-o", os.devnull]
     r = subprocess.run(cmd, capture_output=True, text=True)
     out, cur = {}, None
