@@ -880,7 +880,12 @@ int rr_scene_upload(rr_ctx* c, const rr_scene_desc* d) {
     HIPCHK(upload(c->culls, hs.culls, st));
     HIPCHK(upload(c->inner, hs.inner, st));
     HIPCHK(upload(c->chunks, hs.chunks, st));
-    HIPCHK(upload(c->nodes, hs.nodes, st));
+    {  // the node records, then the planes' normals (rr_device.hpp DevScene.nodes)
+        const size_t nb = hs.nodes.size() * sizeof(rr::DevNode), fb = hs.flat_normal.size() * sizeof(double);
+        HIPCHK(c->nodes.ensure(std::max<size_t>(nb + fb, 16)));
+        if (nb) HIPCHK(hipMemcpyAsync(c->nodes.p, hs.nodes.data(), nb, hipMemcpyHostToDevice, st));
+        if (fb) HIPCHK(hipMemcpyAsync((char*)c->nodes.p + nb, hs.flat_normal.data(), fb, hipMemcpyHostToDevice, st));
+    }
     HIPCHK(upload(c->groups, hs.groups, st));
     HIPCHK(upload(c->shapes, hs.shapes, st));
     HIPCHK(upload(c->tris, hs.tris, st));

@@ -1885,6 +1885,12 @@ struct Comps {
     bool inside;  // Computations.inside (intersection.rs:57-60); read by hit_kernel only
 };
 
+// a plane's record in the table behind the node records (rr_device.hpp DevScene.nodes): its world normal, which
+// depends on the node alone, and [3] != 0 when normal_to_world(nd, (0, 1, 0)) returns exactly these bits here
+// (flat_normal.hpp: the host evaluates this file's sequence next to the reference's)
+__device__ __forceinline__ const double* flat_normal_of(const DevScene& S, int node) {
+    return reinterpret_cast<const double*>(S.nodes + S.n_nodes) + 4 * (int64_t)node;
+}
 // Intersection::prepare_computations (intersection.rs:50-60)
 __device__ __forceinline__ void prepare(const DevScene& S, const Ray& r, const Hit& h, Comps& c) {
     c.point = vadd(r.o, vmul(r.d, h.t));
@@ -1944,6 +1950,105 @@ __device__ __forceinline__ void prepare(const DevScene& S, const Ray& r, const H
     // the hit's T = t |d|_inf within the node's limit (mark_own_safe: the hit point's own rounding)
     c.own_ok = !inside && (nd.flags & NF_OWN_SAFE) &&
                h.t * fmax(fmax(fabs(r.d.x), fabs(r.d.y)), fabs(r.d.z)) <= (double)__int_as_float(nd.aux);
+}
+
+// Hit-uniform tiles (shade_body.inc, the flat fused kernels): all 64 lanes of the wave hit node `node`, a top-level
+// plane (uniform_hit_node; one-sphere tiles measured no separable gain and keep the per-lane code, DESIGN.md §4,
+// tools/patches/uniform_hit_sphere_tiles.patch) whose table entry has the bits this file's normal_to_world gives, so
+// its record, its material and the material's root pattern are read through the constant address space with a uniform index: scalar loads, the records in SGPRs and every kind / flag dispatch
+// a scalar branch, where prepare / material_color gather the same record once per lane.  Per lane the arithmetic is
+// prepare's, material_color's and pattern_at's: the same operations in the same order on the same operands.
+__device__ __forceinline__ bool uniform_hit_node(const DevScene& S, int node) {
+    cptr<DevNode> nd = cp(S.nodes) + node;
+    const int kind = nd->kind;
+    return kind == RR_PLANE && nd->parent < 0 && cp(flat_normal_of(S, node))[3] != 0.0;
+}
+// world_to_object of a top-level node
+__device__ __forceinline__ V3 world_to_object_uniform(cptr<DevNode> nd, V3 p) {
+    const int flags = nd->flags;
+    if (flags & NF_IDENT) return p;
+    if (flags & NF_DIAG) return {nd->inv[0] * p.x + nd->inv[3], nd->inv[5] * p.y + nd->inv[7], nd->inv[10] * p.z + nd->inv[11]};
+    return xf_point(nd->inv, p);
+}
+__device__ __forceinline__ void prepare_uniform(const DevScene& S, const Ray& r, const Hit& h, int node, Comps& c) {
+    cptr<DevNode> nd = cp(S.nodes) + node;
+    c.point = vadd(r.o, vmul(r.d, h.t));
+    c.eyev = vneg(r.d);
+    const int flags = nd->flags;
+    cptr<double> fn = cp(flat_normal_of(S, node));  // normal_to_world(nd, (0, 1, 0)), from the table
+    const V3 nrm = mk(fn[0], fn[1], fn[2]);
+    const bool inside = dot3(nrm, c.eyev) < 0.0;
+    c.inside = inside;
+    c.normalv = inside ? vneg(nrm) : nrm;
+    c.over = vadd(c.point, vmul(c.normalv, RR_EPS));
+    c.under = vsub(c.point, vmul(c.normalv, RR_EPS));
+    c.reflectv = reflect3(r.d, c.normalv);
+    c.n1 = 1.0;
+    c.n2 = 1.0;
+    c.own_ok = !inside && (flags & NF_OWN_SAFE) &&
+               h.t * fmax(fmax(fabs(r.d.x), fabs(r.d.y)), fabs(r.d.z)) <= (double)__int_as_float(nd->aux);
+}
+// prepare of one lane of a UH kernel's tile: a hit-uniform tile reads the node through scalar loads, any other tile
+// takes prepare.  UH false: prepare, as every other kernel calls it.  (A plane lane of a mixed tile reading its normal
+// from the table too measured no gain on C2, DESIGN.md §4, and is not built.)
+template <bool UH>
+__device__ __forceinline__ void prepare_tile(const DevScene& S, const Ray& r, const Hit& h, Comps& c, bool uni, int unode) {
+    if constexpr (UH) {
+        if (uni) {
+            prepare_uniform(S, r, h, unode, c);
+            return;
+        }
+    }
+    prepare(S, r, h, c);
+}
+// the material record light_terms reads: on a hit-uniform tile its four fields from scalar loads
+template <bool UH>
+__device__ __forceinline__ DevMaterial tile_material(const DevScene& S, int mat, bool uni, int umat) {
+    if constexpr (UH) {
+        if (uni) {
+            cptr<DevMaterial> sm = cp(S.mats) + umat;
+            DevMaterial m;
+            m.ambient = sm->ambient;
+            m.diffuse = sm->diffuse;
+            m.specular = sm->specular;
+            m.shininess = sm->shininess;
+            return m;
+        }
+    }
+    return S.mats[mat];
+}
+// material_color for material `mat` of node `node`.  A Stripe / Ring / Checker root whose two children are inline
+// Solids ends here; any other chain goes on per lane, through pattern_at from the root (the same value).
+template <bool CP>
+__device__ __forceinline__ V3 material_color_uniform(const DevScene& S, int mat, int node, V3 over) {
+    cptr<DevMaterial> m = cp(S.mats) + mat;
+    if (m->root == 1) return mk(m->color[0], m->color[1], m->color[2]);
+    const int root = m->pattern;
+    const V3 p = world_to_object_uniform(cp(S.nodes) + node, over);
+    if (root < 0) return mk(1.0, 1.0, 1.0);
+    cptr<DevPattern> P = cp(S.pats) + root;
+    const int kind = P->kind, pf = P->flags;
+    if (kind == RR_PAT_SOLID) return mk(P->color[0], P->color[1], P->color[2]);
+    if ((kind == RR_PAT_STRIPE || kind == RR_PAT_RING || kind == RR_PAT_CHECKER) && (pf & PF_A_SOLID) && (pf & PF_B_SOLID)) {
+        const V3 pp = (pf & NF_IDENT) ? p : xf_point(P->inv, p);
+        bool even;
+        if (kind == RR_PAT_STRIPE) {
+            even = sat_i32(floor(pp.x)) % 2 == 0;
+        } else if (kind == RR_PAT_RING) {
+            even = sat_i32(floor(sqrt(pp.x * pp.x + pp.z * pp.z))) % 2 == 0;
+        } else {
+            even = sat_i32(floor(pp.x) + floor(pp.y) + floor(pp.z)) % 2 == 0;
+        }
+        return even ? mk(P->ca[0], P->ca[1], P->ca[2]) : mk(P->cb[0], P->cb[1], P->cb[2]);
+    }
+    return pattern_at<CP>(S, root, p, node);
+}
+template <bool UH, bool CP>
+__device__ __forceinline__ V3 tile_color(const DevScene& S, const DevMaterial& m, int node, V3 over, bool uni, int umat) {
+    if constexpr (UH) {
+        if (uni) return material_color_uniform<CP>(S, umat, uniform(node), over);
+    }
+    return material_color<CP>(S, m, node, over);
 }
 
 // The hit node a lane's shadow rays toward a light may skip, or -1.  A convex leaf (sphere, plane) hit from outside

@@ -6,6 +6,8 @@
 // concatenation reproduces), so "earliest node index" is the reference's tie-break.
 #include "flatten.hpp"
 
+#include "flat_normal.hpp"
+
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -847,6 +849,15 @@ int flatten_scene(const rr_scene_desc& d, HostScene& out, std::string& err) {
     out.tri_inline = n_tri > 0 && n_inline == n_tri ? 1 : 0;
     mark_own_safe(out);
     mark_inner_balls(out);
+    // every plane's world normal (flat_normal.hpp), from the records as the kernels will read them, and whether the
+    // kernels' own arithmetic gives its bits (the record's fourth value); other kinds keep zeros: not usable
+    static_assert(FN_DIAG == NF_DIAG && FN_TRI_INLINE == NF_TRI_INLINE, "flat_normal.hpp restates these flags");
+    out.flat_normal.assign(FLAT_NORMAL_STRIDE * out.nodes.size(), 0.0);
+    for (size_t ni = 0; ni < out.nodes.size(); ++ni)
+        if (out.nodes[ni].kind == RR_PLANE) {
+            double* e = &out.flat_normal[FLAT_NORMAL_STRIDE * ni];
+            e[3] = flat_plane_normal(out.nodes.data(), (int32_t)ni, e) ? 1.0 : 0.0;
+        }
     for (DevChunk& ch : out.chunks) {  // runs of one kind (DevChunk.run)
         ch.run = CR_NONE;
         const DevNode& a = out.nodes[ch.start];

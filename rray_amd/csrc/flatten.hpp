@@ -12,6 +12,7 @@ struct HostScene {
     std::vector<DevNode> nodes;
     std::vector<DevCull> culls;  // one per node
     std::vector<DevCull> inner;  // one per node: a ball inside the set the node's exact test reports (r 0: none)
+    std::vector<double> flat_normal;  // four per node: a plane's world normal and whether kernels may read it (flat_normal.hpp)
     std::vector<DevChunk> chunks;
     std::vector<DevGroup> groups;
     std::vector<DevTri> tris;

@@ -85,6 +85,10 @@ struct LevelArgs {
     // the struct, so that no other field moves in the kernels that never read them.
     const uint32_t* list;
     uint32_t list_w;
+    // the flat fused level-0 kernels (shade_body.inc UH): the scalar path for hit-uniform tiles, planes' normals from
+    // the table behind DevScene.nodes.  Set by their launches (render_levels.inc uniform_hit_on); RRAY_NO_UNIFORM_HIT=1
+    // keeps the per-lane code, for tests and same-binary timing.  In the struct's tail padding: no field moves.
+    uint32_t uniform_hit;
 };
 
 struct CombArgs {

@@ -884,6 +884,12 @@ static void launch_shade(const DevScene& S, const LevelArgs& A, hipStream_t st, 
     }
 }
 
+// LevelArgs.uniform_hit of a launch: on unless RRAY_NO_UNIFORM_HIT=1 (read at every launch, like RRAY_NO_PERSIST)
+static inline uint32_t uniform_hit_on() {
+    const char* off = std::getenv("RRAY_NO_UNIFORM_HIT");
+    return (off && std::atoi(off) == 1) ? 0u : 1u;
+}
+
 template <int G, bool LC>
 void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     const bool pre = S.n_lights <= RR_PRELIT_LIGHTS;
@@ -891,7 +897,13 @@ void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
                              (S.has_area ? sizeof(AreaStage) : 0);
     if (fused_levels(S)) {  // trace + shade in one kernel
         Span s(prof, K_TRACE_SHADE, st);
-        launch_shade<G, LC, true>(S, A, st, pre, shade_lds);
+        if constexpr (G == 0 && !LC) {  // the kernels that read it (shade_body.inc UH)
+            LevelArgs B = A;
+            B.uniform_hit = uniform_hit_on();
+            launch_shade<G, LC, true>(S, B, st, pre, shade_lds);
+        } else {
+            launch_shade<G, LC, true>(S, A, st, pre, shade_lds);
+        }
         return;
     }
 #ifndef RR_LISTED  // the listed-pixel kernels serve the production dispatches only: no unfused level kernels

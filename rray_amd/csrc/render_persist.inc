@@ -154,6 +154,7 @@ void launch_persist_t(const DevScene& S, const LevelArgs& A, const PersistPlan& 
                   "persist_args: plain structures at their natural offsets");
     LevelArgs B = A;
     B.persist_heads = plan.heads;
+    B.uniform_hit = uniform_hit_on();
     Span s(prof, K_TRACE_SHADE, st);
     hipLaunchKernelGGL((persist_kernel<G, LC, true, true, false, false, false>), dim3((unsigned)plan.blocks), dim3(256),
                        persist_lds(S), st, S, B);

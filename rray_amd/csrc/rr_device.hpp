@@ -137,7 +137,11 @@ struct DevScene {
     const DevCull* culls;
     const DevCull* inner;     // per node: a ball inside what its exact test reports (spheres; r == 0: none)
     const DevChunk* chunks;
-    const DevNode* nodes;
+    const DevNode* nodes;     // n_nodes records, then four doubles per node: a plane's world normal, which no hit
+                              // changes, and whether the kernels' normal_to_world gives its bits (flat_normal.hpp);
+                              // read by the flat fused kernels only (device_core.inc flat_normal_of).  In the nodes'
+                              // buffer and not behind a pointer of its own: a DevScene 8 bytes larger moved the scratch
+                              // size of 196 kernels
     const DevGroup* groups;
     const DevTri* tris;
     const DevMaterial* mats;

@@ -6,6 +6,15 @@
 // The including scope provides: template parameters G, LC, FUSED, PRE, CP, RM, AR; S, A; the event index iu / i and
 // `valid`; ORD; clk0 (the wave's clock at entry, cost-ordered kernels); cnt, trace_flops, trace_visits (zero); and
 // `tile`: the level-0 tile the wave renders, or -1 for the tile of its launch slot.
+    // UH: the C2 family (flat scene, global culls, fused, prelit point lights, no tree pattern: persist_kernel and the
+    // level-0 shade_kernel it mirrors) shades a tile whose 64 lanes hit one node from scalar records, a plane's normal
+    // from the table behind S.nodes (device_core.inc prepare_tile / tile_material / tile_color); every other
+    // instantiation compiles to the code it had
+#ifdef RR_LISTED
+    constexpr bool UH = false;
+#else
+    constexpr bool UH = G == 0 && !LC && FUSED && PRE && !CP && !RM && !AR;
+#endif
     const Px0 q0 = level0_px_if<true, ORD>(A, i, tile);
     const uint32_t ls0 = q0.ls;
     HitRec hr;
@@ -32,6 +41,15 @@
         hr = A.hit[i];
     }
     const bool has_hit = valid && hr.node >= 0;
+    // UH: every lane of the wave is valid and hit the same top-level plane (partial and mixed tiles keep
+    // the per-lane code); unode / umat are wave-uniform then
+    bool uni = false;
+    int unode = 0, umat = 0;
+    if constexpr (UH) {
+        unode = uniform(hr.node);
+        umat = uniform(hmat);
+        uni = A.uniform_hit && __ballot(has_hit && hr.node == unode) == ~0ull && uniform_hit_node(S, unode);
+    }
     int32_t parent = -1, slot = 0;
     if (valid && A.level > 0) {
         parent = A.ev[i].parent;
@@ -57,7 +75,7 @@
         mat = (FUSED && !AR) ? hmat : S.nodes[hr.node].material;
         const DevMaterial m = S.mats[mat];
         Comps c;
-        prepare(S, r, h, c);  // intersection.rs:50-60
+        prepare_tile<UH>(S, r, h, c, uni, unode);  // intersection.rs:50-60
         if (S.has_transparent && needs_n1n2(m, A.rem)) {
             c.n1 = A.n12[2 * i];
             c.n2 = A.n12[2 * i + 1];
@@ -152,8 +170,8 @@
     // pattern and `pow` code below the 128-VGPR budget without spilling
     constexpr int NPL = prelit_per_light(AR);
     if (has_hit) {
-        const DevMaterial m = S.mats[mat];
-        pcol = material_color<CP>(S, m, hr.node, over);  // material.rs:77-80
+        const DevMaterial m = tile_material<UH>(S, mat, uni, umat);
+        pcol = tile_color<UH, CP>(S, m, hr.node, over, uni, umat);  // material.rs:77-80
         if (PRE) {
             double* pl = prelit_lds(S, LC);
             for (int li = 0; li < S.n_lights; ++li) {
