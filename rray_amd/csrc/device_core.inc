@@ -2081,12 +2081,12 @@ __device__ __forceinline__ int reflect_own(const Comps& c, int own) {
 // same operations in the same order, so the shadow walk can run without eyev / normalv / colour
 // live.  `color` = pattern_at_object(obj, over_point).
 // f64::powf(x, y) (libm pow: correctly rounded but for rare near-halfway cases) for the specular factor.
-// When every active lane has x > 0 and the same integer exponent n in [1, 512] (shininess 200 in the
+// For the lanes with 0 < x <= 2^500 and the wave's integer exponent n in [1, 512] (shininess 200 in the
 // benchmark scenes): x = m 2^e (frexp, m in [0.5, 1)), m^n by squaring in double-double with fma
 // (relative error < 2^-98, so the rounded high part is the correctly rounded m^n but for inputs within
 // 2^-98 of a rounding midpoint), scaled by 2^(e n) (exact unless the result is subnormal, < 2.2e-308).
 // ~65 vector instructions instead of OCML's ~200, and closer to libm (OCML pow is within 1 ulp).
-// Other waves take OCML pow.
+// Other lanes take OCML pow.
 __device__ __forceinline__ void dd_mul(double& ah, double& al, double bh, double bl) {
     const double p = ah * bh;
     double e = __builtin_fma(ah, bh, -p);
@@ -2104,10 +2104,7 @@ __device__ __forceinline__ void dd_sqr(double& ah, double& al) {
     al = e - (s - p);
     ah = s;
 }
-__device__ __forceinline__ double pow_shininess(double x, double y) {
-    const int n0 = __builtin_amdgcn_readfirstlane((int)fmin(fmax(y, 0.0), 1024.0));
-    const bool fast = x > 0.0 && x <= 0x1p500 && y == (double)n0 && n0 >= 1 && n0 <= 512;
-    if (__ballot(!fast) != 0) return pow(x, y);
+__device__ __forceinline__ double pow_int_dd(double x, int n0) {  // x in (0, 2^500], n0 in [1, 512] wave-uniform
     int e;
     const double m = frexp(x, &e);
     double rh = 1.0, rl = 0.0, bh = m, bl = 0.0;
@@ -2129,6 +2126,17 @@ __device__ __forceinline__ double pow_shininess(double x, double y) {
         dd_sqr(bh, bl);
     }
     return ldexp(rh, e * n0);
+}
+__device__ __forceinline__ double pow_shininess(double x, double y) {
+    const int n0 = __builtin_amdgcn_readfirstlane((int)fmin(fmax(y, 0.0), 1024.0));
+    const bool fast = x > 0.0 && x <= 0x1p500 && y == (double)n0 && n0 >= 1 && n0 <= 512;
+    if (__ballot(!fast) == 0) return pow_int_dd(x, n0);
+    // a lane outside the fast domain (a NaN or infinite x beside ordinary lanes: the NaN normal at a cone's apex)
+    // takes OCML pow by itself; the other lanes of its wave keep the correctly rounded power
+    const double p = pow(x, y);
+    if (__ballot(fast) == 0) return p;
+    const double r = pow_int_dd(fast ? x : 1.0, n0);
+    return fast ? r : p;
 }
 
 // dir_out (optional, LDS [4][256] doubles at this thread): normalize(light - point) and |light - point| — is_shadowed's

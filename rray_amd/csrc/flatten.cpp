@@ -493,6 +493,20 @@ int flatten_scene(const rr_scene_desc& d, HostScene& out, std::string& err) {
             err = "pattern nesting exceeds RR_MAX_PATTERN_DEPTH";
             return RR_E_LIMIT;
         }
+    // A Perturbed node hands its subtree a point that is no longer finite once the noise overflows (lattice
+    // coordinates past 2^31, noise.rs over `as i32`).  The reference multiplies that point by every descendant's
+    // inverse, the identity included, where 0 * inf is NaN (pattern.rs:145-147): those descendants keep the
+    // multiplication (for a finite point it returns the point, as the shortcut does).
+    std::function<void(int, bool)> below_perturbed = [&](int i, bool below) {
+        DevPattern& p = out.pats[i];
+        if (below) p.flags &= ~NF_IDENT;
+        if (p.kind == RR_PAT_TEST || p.kind == RR_PAT_SOLID || p.kind == RR_PAT_TEXTURE) return;
+        below = below || p.kind == RR_PAT_PERTURBED;
+        below_perturbed(p.a, below);
+        if (p.kind != RR_PAT_PERTURBED) below_perturbed(p.b, below);
+    };
+    for (int i = 0; i < d.n_patterns; ++i)
+        if (out.pats[i].kind == RR_PAT_PERTURBED) below_perturbed(i, false);
     // textures
     if (d.n_textures < 0 || (d.n_textures > 0 && (!d.tex_size || !d.texels))) {
         err = "texture arrays missing";
@@ -783,6 +797,23 @@ int flatten_scene(const rr_scene_desc& d, HostScene& out, std::string& err) {
             world = multiply(world, inverse(nfull));
         }
         out.culls[ni] = make_cull(world, lc, lr);
+        // Cones and tori: the reference reports hits of these two far outside their AABB.  A cone ray with
+        // |a| < EPSILON takes t = -c / (2 b) (cone.rs:96-103), half the distance to the infinite cone, wherever that
+        // is; a torus ray from an origin 1e5 tube sizes away has quartic coefficients (torus.rs:37-95) that cancel to
+        // noise, and find_roots_quartic returns roots anywhere along it, +inf included.  The reference tests such a
+        // leaf exactly when the boxes of the groups around it are hit (group.rs:80-91: a line test, tmin <= tmax, with
+        // no sign or distance bound; a CSG tests no box, csg.rs:105-113).  No sphere stands for that: the forward and
+        // segment culls also reject a sphere behind the origin, beyond the closest hit or beyond the light, where
+        // such hits may lie.  So the leaf and every container above it are unbounded: each lane runs the groups'
+        // exact box tests (a group visited by every lane sets skip_until for the lanes that miss its box) and is
+        // handed the leaf exactly when they pass.
+        bool wide = nd.kind == RR_CONE || nd.kind == RR_TORUS;
+        if (is_container(nd.kind))
+            for (int j = (int)ni + 1; j < nd.skip; ++j) wide = wide || out.nodes[j].kind == RR_CONE || out.nodes[j].kind == RR_TORUS;
+        if (wide) {
+            out.culls[ni] = DevCull{};
+            out.culls[ni].r = std::numeric_limits<float>::infinity();
+        }
     }
     // CSG filtering needs left.includes(leaf) for every CSG above a leaf (csg.rs:86-88): leaves compare
     // ids, groups ask all children (group.rs:151-159), a CSG only its two direct children (csg.rs:160-162)

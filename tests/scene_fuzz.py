@@ -31,6 +31,10 @@ CATEGORIES = ["scales", "far_cam", "tiny_far", "groups", "grazing", "lights", "m
 SHININESS = 200.0
 
 
+class Pat(tuple):
+    """(builder pattern id, oracle pattern id) of one pattern tree node; accepted wherever a colour is."""
+
+
 class Pair:
     """One scene on both sides: product SceneBuilder + oracle.Oracle, identical inputs."""
 
@@ -45,6 +49,8 @@ class Pair:
         self.log = []  # printable description (failing seeds print it)
 
     def _mat(self, m7, color):
+        if isinstance(color, Pat):  # a pattern tree built with pat(): (builder id, oracle id)
+            return color
         pb = self.b.pattern("solid", color=color)
         po = self.o.pattern("solid", color=color)
         return pb, po
@@ -79,15 +85,61 @@ class Pair:
                         f"tr={np.round(tr, 6).tolist()} mat={m7}")
         return bid
 
-    def triangle(self, p1, p2, p3, m7, color, parent=-1, normals=None):
+    def cone(self, tr, m7, color, minimum, maximum, closed, parent=-1):
+        pb, po = self._mat(m7, color)
+        bid = self.b.cone(minimum, maximum, closed, transform=tr, material=m7, pattern=pb, parent=parent)
+        oid = self.o.add("cone", self.ids[parent] if parent >= 0 else -1, tr, m7, po)
+        self.o.set_shape_params(oid, minimum, maximum, closed)
+        self.ids[bid] = oid
+        self.log.append(f"cone id={bid} parent={parent} [{minimum},{maximum}] closed={closed} "
+                        f"tr={np.round(tr, 6).tolist()} mat={m7}")
+        return bid
+
+    def torus(self, tr, m7, color, minor_radius, parent=-1):
+        pb, po = self._mat(m7, color)
+        bid = self.b.torus(minor_radius, transform=tr, material=m7, pattern=pb, parent=parent)
+        oid = self.o.add("torus", self.ids[parent] if parent >= 0 else -1, tr, m7, po)
+        self.o.set_shape_params(oid, minor_radius, math.inf, False)  # scene_builder_yaml.rs:350-353
+        self.ids[bid] = oid
+        self.log.append(f"torus id={bid} parent={parent} r={minor_radius} tr={np.round(tr, 6).tolist()} mat={m7}")
+        return bid
+
+    def csg(self, op, tr, parent=-1):
+        """A CSG node; its left then its right child are the next two objects added with parent=<this id>."""
+        bid = self.b.csg(op, transform=tr, parent=parent)
+        oid = self.o.add_csg(op, self.ids[parent] if parent >= 0 else -1, tr)
+        self.ids[bid] = oid
+        self.log.append(f"csg {op} id={bid} parent={parent} tr={np.round(tr, 6).tolist()}")
+        return bid
+
+    def pat(self, kind, color=(0.0, 0.0, 0.0), a=None, b=None, scale=0.5, transform=None, octaves=1, persistence=1.0):
+        """One pattern tree node on both sides; a and b are Pat pairs (for "texture", a is a tex() pair)."""
+        tr = transform if transform is not None else self.M.identity()
+        a, b = a or (-1, -1), b or (-1, -1)
+        pb = self.b.pattern(kind, color=color, a=a[0], b=b[0], scale=scale, transform=tr, octaves=octaves,
+                            persistence=persistence)
+        po = self.o.pattern(kind, color=color, a=a[1], b=b[1], scale=scale, transform=tr)
+        if kind in ("perturbed", "noise"):
+            self.o.set_noise(po, octaves, persistence)
+        self.log.append(f"pattern {kind} ids=({pb},{po}) color={color} a={tuple(a)} b={tuple(b)} scale={scale} "
+                        f"octaves={octaves} persistence={persistence} tr={np.round(tr, 6).tolist()}")
+        return Pat((pb, po))
+
+    def tex(self, rgba):
+        """An RGBA8 image (height, width, 4) on both sides -> (builder index, oracle index)."""
+        return Pat((self.b.texture(rgba), self.o.add_texture(rgba)))
+
+    def triangle(self, p1, p2, p3, m7, color, parent=-1, normals=None, tr=None):
         pb, po = self._mat(m7, color)
         op = self.ids[parent] if parent >= 0 else -1
         if normals is None:
-            bid = self.b.triangle(p1, p2, p3, material=m7, pattern=pb, parent=parent)
+            bid = self.b.triangle(p1, p2, p3, transform=tr, material=m7, pattern=pb, parent=parent)
             oid = self.o.add_triangle(p1, p2, p3, op)
         else:
-            bid = self.b.smooth_triangle(p1, p2, p3, *normals, material=m7, pattern=pb, parent=parent)
+            bid = self.b.smooth_triangle(p1, p2, p3, *normals, transform=tr, material=m7, pattern=pb, parent=parent)
             oid = self.o.add_smooth_triangle(p1, p2, p3, *normals, parent=op)
+        if tr is not None:
+            self.o.set_transform(oid, tr)
         self.o.set_material(oid, m7, po)
         self.ids[bid] = oid
         self.log.append(f"{'smooth_' if normals else ''}triangle id={bid} parent={parent} "
@@ -416,6 +468,141 @@ def build_own(seed):
     P.log.append(f"camera from={frm} to={to} fov={fov} depth={depth}")
     return P, {"from_": tuple(float(x) for x in frm), "to": tuple(float(x) for x in to), "up": (0.0, 1.0, 0.0),
                "fov": float(fov)}, depth, cat
+
+
+GENERAL = ["cones", "tori", "csg", "patterns", "textures", "mixed"]
+GENERAL_SEEDS = range(48)
+
+
+def _pattern_tree(P, rng, level=0):
+    """a random pattern tree with its own transforms: stripe / gradient / ring / checker / blend / perturbed / noise over
+    solids, nested up to three levels"""
+    M = P.M
+    if level >= 3 or (level > 0 and rng.random() < 0.4):
+        return P.pat("solid", _color(rng))
+    kind = str(rng.choice(["stripe", "gradient", "ring", "checker", "blend", "perturbed", "noise"]))
+    tr = _mul(M, M.scale(*[_logu(rng, 0.2, 2.0) for _ in range(3)]), _rot(M, rng),
+              M.translate(*[float(x) for x in rng.uniform(-1, 1, 3)])) if rng.random() < 0.7 else None
+    a = _pattern_tree(P, rng, level + 1)
+    if kind == "perturbed":
+        return P.pat(kind, a=a, scale=float(rng.uniform(0.05, 0.6)), transform=tr, octaves=int(rng.integers(1, 9)),
+                     persistence=float(rng.choice([0.3, 0.5, 1.0, 2.0])))
+    b = _pattern_tree(P, rng, level + 1)
+    if kind == "noise":
+        return P.pat(kind, a=a, b=b, scale=float(rng.uniform(0.5, 3.0)), transform=tr, octaves=int(rng.integers(1, 9)),
+                     persistence=float(rng.choice([0.3, 0.5, 1.0, 2.0])))
+    return P.pat(kind, a=a, b=b, scale=float(rng.uniform(0.0, 1.0)), transform=tr)
+
+
+def build_general(seed):
+    """Scenes for the general kernels (the G = 2 variant: EntriesT<4>, csg_eval, quartic.inc, pattern_tree, texture_at),
+    families by seed % 6:
+
+      cones     closed, open and one-sided cones, non-uniformly scaled, half of them in sheared groups
+      tori      tori of minor radius 0.05-1.5 at scales 1e-3 to 1e3, seen from 12 to 1e5 scene sizes away
+      csg       nested CSG trees (depth <= 3, groups as children, cone / cylinder / torus children, at most
+                RR_MAX_CSG_ENTRIES possible entries), glass among the leaves, a glass sphere beside them
+      patterns  random pattern trees with their own transforms on every shape kind and on the floor
+      textures  numpy textures of 1-6 x 1-6 texels on every shape kind
+      mixed     everything inside sheared groups, reflective and glass materials, recursion depth 5
+
+    -> (Pair, camera spec, max_depth, family); Pair.featured holds the builder ids of the family's featured leaves."""
+    rng = np.random.default_rng(40_000 + seed)
+    cat = GENERAL[seed % len(GENERAL)]
+    P = Pair()
+    M = P.M
+    P.featured = set()
+    depth = 5 if cat in ("mixed", "csg") else 3
+    s = 1.0  # scene scale
+    frm, to, fov = (float(rng.uniform(-6, 6)), float(rng.uniform(2, 8)), -14.0), (0.0, 0.0, 0.0), float(rng.uniform(0.7, 1.0))
+
+    def place(size=(0.4, 1.6), spread=4.0):
+        return _mul(M, M.scale(*[s * _logu(rng, *size) for _ in range(3)]), _rot(M, rng),
+                    M.translate(*[float(x) for x in rng.uniform(-spread, spread, 3) * [s, 0.5 * s, s]]))
+
+    def sheared_group(parent=-1):
+        return P.obj("group", _mul(M, M.scale(*rng.uniform(0.6, 1.6, 3)), M.shear(*[float(x) for x in rng.uniform(-0.6, 0.6, 6)]),
+                                   _rot(M, rng), M.translate(*[float(x) for x in rng.uniform(-1.5, 1.5, 3) * s])), parent=parent)
+
+    def leaf(kind, tr, m7, col, parent=-1):
+        if kind == "cone":
+            lo = float(rng.uniform(-2, 0))
+            onesided = rng.random() < 0.2
+            i = P.cone(tr, m7, col, -math.inf if onesided else lo, lo + float(rng.uniform(0.2, 2.5)),
+                       bool(rng.random() < 0.6) and not onesided, parent)
+        elif kind == "cylinder":
+            lo = float(rng.uniform(-2, 0))
+            i = P.cylinder(tr, m7, col, lo, lo + float(rng.uniform(0.2, 3)), bool(rng.random() < 0.6), parent)
+        elif kind == "torus":
+            i = P.torus(tr, m7, col, float(rng.choice([0.05, 0.25, 0.5, 0.9, 1.0, 1.5])), parent)
+        elif kind == "triangle":
+            pts = [tuple(float(x) for x in rng.uniform(-1, 1, 3)) for _ in range(3)]
+            nrm = [tuple(float(x) for x in _unit(rng)) for _ in range(3)] if rng.random() < 0.5 else None
+            i = P.triangle(*pts, m7, col, parent=parent, normals=nrm, tr=tr)
+        else:
+            i = P.obj(kind, tr, m7, col, parent)
+        return i
+
+    def csg_tree(parent, level, tr, glass_p):
+        c = P.csg(str(rng.choice(["union", "intersection", "difference"])), tr, parent)
+        for _ in range(2):
+            r = rng.random()
+            small = _mul(M, M.scale(*rng.uniform(0.6, 1.3, 3)), _rot(M, rng), M.translate(*[float(x) for x in rng.uniform(-0.6, 0.6, 3)]))
+            if level < 3 and r < 0.35:
+                csg_tree(c, level + 1, small, glass_p)
+            elif level < 3 and r < 0.45:
+                g = P.obj("group", small, parent=c)
+                for _ in range(2):
+                    P.featured.add(leaf(str(rng.choice(["sphere", "cube", "cone"])), place((0.5, 1.2), 0.5),
+                                        _material(rng, 0.3, glass_p), _color(rng), g))
+            else:
+                P.featured.add(leaf(str(rng.choice(["sphere", "cube", "cylinder", "cone", "torus"])), small,
+                                    _material(rng, 0.3, glass_p), _color(rng), c))
+        return c
+
+    if cat == "tori":
+        s = _logu(rng, 1e-3, 1e3)
+        for _ in range(int(rng.integers(4, 9))):
+            P.featured.add(leaf("torus", place((0.8, 2.5), 3.0), _material(rng), _color(rng)))
+        dist = s * float(rng.choice([12.0, 1e3, 1e5]))
+        frm = tuple(float(x) for x in _unit(rng) * [1, 0.5, 1] * dist + [0, 0.4 * dist, 0])
+        fov = float(2.0 * math.atan(7.0 * s / np.linalg.norm(frm)))
+    elif cat == "cones":
+        for _ in range(int(rng.integers(6, 14))):
+            parent = sheared_group() if rng.random() < 0.5 else -1
+            P.featured.add(leaf("cone", place(), _material(rng), _color(rng), parent))
+    elif cat == "csg":
+        for _ in range(int(rng.integers(3, 6))):
+            parent = sheared_group() if rng.random() < 0.3 else -1
+            csg_tree(parent, 1, place((0.8, 1.8), 3.5), 0.35)
+        P.obj("sphere", place((0.8, 1.5), 2.0), (0.1, 0.4, 0.9, SHININESS, 0.1, 0.9, 1.5), _color(rng))
+    elif cat == "patterns":
+        for k in ("sphere", "cube", "cylinder", "cone", "torus", "triangle", "sphere", "cube")[:int(rng.integers(5, 9))]:
+            P.featured.add(leaf(k, place((0.7, 2.0)), _material(rng), _pattern_tree(P, rng)))
+    elif cat == "textures":
+        for k in ("sphere", "cube", "cylinder", "cone", "torus", "triangle", "sphere", "cube")[:int(rng.integers(5, 9))]:
+            img = rng.integers(0, 256, (int(rng.integers(1, 7)), int(rng.integers(1, 7)), 4), dtype=np.uint8)
+            pat = P.pat("texture", a=P.tex(img), transform=M.scale(*rng.uniform(0.5, 2, 3)) if rng.random() < 0.5 else None)
+            P.featured.add(leaf(k, place((0.7, 2.0)), _material(rng), pat))
+    else:  # mixed
+        for _ in range(int(rng.integers(2, 5))):
+            g = sheared_group()
+            for _ in range(int(rng.integers(2, 5))):
+                r = rng.random()
+                if r < 0.25:
+                    csg_tree(g, 2, place((0.6, 1.4), 2.0), 0.3)
+                else:
+                    k = str(rng.choice(["sphere", "cube", "cylinder", "cone", "torus", "triangle"]))
+                    col = _pattern_tree(P, rng) if rng.random() < 0.4 else _color(rng)
+                    P.featured.add(leaf(k, place((0.5, 1.5), 2.0), _material(rng, 0.5, 0.3), col, g))
+    floor_col = _pattern_tree(P, rng) if cat in ("patterns", "mixed") else _color(rng)
+    floor = P.obj("plane", M.translate(0.0, -3.0 * s, 0.0), _material(rng, 0.4 if cat == "mixed" else 0.0), floor_col)
+    if cat == "patterns":
+        P.featured.add(floor)
+    P.light(rng.uniform(-20, 20, 3) * s + [0, 25 * s, -10 * s])
+    up = (0.0, 1.0, 0.0)
+    P.log.append(f"camera from={frm} to={to} up={up} fov={fov} depth={depth}")
+    return P, {"from_": tuple(float(x) for x in frm), "to": to, "up": up, "fov": fov}, depth, cat
 
 
 def cameras(P, spec, W, H):

@@ -182,6 +182,39 @@ def test_fuzz_scene_hits_equal_the_oracle(R, renderer, seed):
         raise
 
 
+@pytest.mark.parametrize("seed", range(24))
+def test_general_fuzz_scene_hits_equal_the_oracle(R, renderer, seed):
+    """scene_fuzz.build_general(seed), every family four times (cones, tori, CSG, patterns, textures, mixed), 33 x 17
+    samples: hit_at on the camera's rays and the render_aov planes against the oracle's hit + prepare_computations
+    of every sample.  Seeds 1 and 19 hold the reference's spurious far-torus roots."""
+    import oracle
+
+    P, spec, _, cat = F.build_general(seed)
+    Hs, V = 33, 17
+    cam, ocam = F.cameras(P, spec, Hs, V)
+    renderer.upload(P.b)
+    rays = camera_rays(oracle, ocam)
+    want = oracle_hits(R, P.o, rays, {v: k for k, v in P.ids.items()})
+    got = renderer.hit_at(*batch(rays))
+    st = renderer.last_stats()
+    try:
+        assert_records_equal(got, want, f"general seed {seed} ({cat}) hit_at")
+        hits = int((want["object"] >= 0).sum())
+        assert (st["rays"], st["samples"], st["n1n2_scans"]) == (Hs * V, Hs * V, hits), st
+        assert st["shadow_rays"] == 0 and st["shade_events"] == 0 and st["nan_rays"] == 0
+        aov = renderer.render_aov(cam, planes=("depth", "normal", "object"))
+        depth, normal, obj = planes_of(want, V, Hs)
+        assert same(aov["object"], obj), f"seed {seed} ({cat}): object plane"
+        assert same(aov["depth"], depth), f"seed {seed} ({cat}): depth plane"
+        assert same(aov["normal"], normal), f"seed {seed} ({cat}): normal plane"
+        s2 = aov["stats"]
+        assert (s2["rays"], s2["samples"], s2["n1n2_scans"], s2["shadow_rays"], s2["shade_events"]) == \
+            (Hs * V, Hs * V, 0, 0, 0), s2
+    except AssertionError:
+        print("\n".join(P.log))
+        raise
+
+
 def _albedo_pair(R):
     """A checker floor, a striped transformed sphere inside a scaled group and a solid sphere, through the product's
     SceneBuilder and the oracle side by side -> (builder, oracle, camera transform, {builder id: oracle id},
