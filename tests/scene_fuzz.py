@@ -612,3 +612,211 @@ def cameras(P, spec, W, H):
 
     t = P.M.view_transform(spec["from_"], spec["to"], spec["up"])
     return R.camera(W, H, spec["fov"], t), oracle.Oracle.camera(W, H, spec["fov"], t)
+
+
+# --- the production dispatch paths (tests/test_gpu_fuzz_paths.py, tests/test_fuzz_paths_host.py) -------------------
+
+BUILDERS = {"build": build, "general": build_general, "area": build_area, "own": build_own}
+# the first two seeds of every category of every builder: 8, 6, 4 and 6 categories
+PATH_SCENES = ([("build", s) for s in range(16)] + [("general", s) for s in range(12)] +
+               [("area", s) for s in range(8)] + [("own", s) for s in range(12)])
+PATH_IDS = [f"{b}-{s}" for b, s in PATH_SCENES]
+PRELIT_LIGHTS = 2  # kernels.hpp RR_PRELIT_LIGHTS: the resident tile loop's kernel holds at most two lights' terms
+QUERY_SIZE = (33, 17)  # the query batch's camera: partial tiles on both edges
+QUERY_PREFIXES = (1, 63, 65, 257)
+
+
+def build_path(name, seed):
+    """-> (Pair, camera spec, max_depth, category, jitter seed) of one PATH_SCENES entry"""
+    P, spec, depth, cat = BUILDERS[name](seed)
+    return P, spec, depth, cat, seed
+
+
+def traits(P):
+    """What the dispatch of api.cpp reads, from the builder's descriptor alone (flatten.cpp: has_transparent,
+    max_children, groups, has_csg / has_quad; api.cpp rr_scene_upload: has_groups, general, has_area).  flat: the
+    G == 0 kernels; loop: the resident tile loop may serve a depth-0 frame of full tiles under global culls
+    (render_persist.inc persist_plan_t, render_persist_g0_gl.hip)."""
+    import rray_amd as R
+
+    L = R._lib
+    b = P.b
+    mats = np.array(b.mats).reshape(-1, 7)
+    kinds = set(b.kind)
+    t = {"reflective": bool((mats[:, 4] != 0.0).any()), "transparent": bool((mats[:, 5] != 0.0).any()),
+         "groups": bool(kinds & {L.GROUP, L.CSG}),
+         "general": bool(kinds & {L.CUBE, L.CYLINDER, L.CONE, L.TORUS, L.CSG}),
+         "area": L.LIGHT_AREA in b.light_kind, "lights": len(b.light_kind),
+         "solid_patterns": all(k == L.PAT["solid"] for k in b.pat_kind)}
+    t["flat"] = not t["groups"] and not t["general"] and not t["transparent"]
+    t["loop"] = t["flat"] and not t["area"] and t["lights"] <= PRELIT_LIGHTS and t["solid_patterns"]
+    return t
+
+
+def oracle_frame(P, ocam, depth, seed=0, libm=False):
+    """The oracle's canvas and counters with correctly rounded powers; libm: also with libm's pow, the
+    reference's own arithmetic -> (canvas_cr, st_cr) or (canvas_cr, st_cr, (canvas, st))."""
+    if libm:
+        ref = P.o.render(ocam, max_depth=depth, seed=seed)
+    P.o.set_pow_mode(1)
+    try:
+        canvas_cr, st_cr = P.o.render(ocam, max_depth=depth, seed=seed)
+    finally:
+        P.o.set_pow_mode(0)
+    return (canvas_cr, st_cr, ref) if libm else (canvas_cr, st_cr)
+
+
+def oracle_counts(st):
+    """the oracle's counters under the product's names (its rays include the shadow rays)"""
+    return {"rays": st["rays"] - st["shadow_rays"], "shadow_rays": st["shadow_rays"], "shade_events": st["shade_events"]}
+
+
+def check_frame(got, P, what, canvas_cr, st_cr, libm=None):
+    """The exact-cull comparison of one rendered frame: the canvas equals the oracle's (correctly rounded powers) bit for
+    bit and rays / shadow_rays / shade_events equal the oracle's.  libm=(canvas, st) of the libm-pow oracle: its counters
+    equal the other oracle's, and the frame may differ from it only in samples where the two oracles differ.  A failure
+    prints the differing samples and the scene."""
+    diff = np.argwhere((got["canvas"] != canvas_cr).any(axis=2))
+    counts = {k: (got["stats"][k], v) for k, v in oracle_counts(st_cr).items()}
+    ok = len(diff) == 0 and all(a == b for a, b in counts.values())
+    pow_only = []
+    if libm is not None:
+        canvas, st = libm
+        pow_only = np.argwhere((got["canvas"] != canvas).any(axis=2))
+        oracles_differ = (canvas != canvas_cr).any(axis=2)
+        ok = ok and st == st_cr and all(oracles_differ[y, x] for y, x in pow_only)
+    if not ok:
+        print(f"{what}: {len(diff)} samples differ from the correctly rounded oracle, {len(pow_only)} from the libm one; "
+              f"counts (gpu, oracle) {counts}")
+        for y, x in diff[:10]:
+            print(f"  sample ({x},{y}): gpu {got['canvas'][y, x].tolist()} oracle {canvas_cr[y, x].tolist()}")
+        print("\n".join(P.log))
+    elif len(pow_only):
+        print(f"{what}: {len(pow_only)} samples differ from libm pow by its rounding only")
+    assert ok, what
+
+
+def first_hits(P, ocam):
+    """(vsize, hsize) oracle object id of every sample's first entry with t >= 0 (intersection.rs hit()); -1: a miss"""
+    import oracle
+
+    out = np.full((ocam.vsize, ocam.hsize), -1, np.int64)
+    for y in range(ocam.vsize):
+        for x in range(ocam.hsize):
+            ro, rd = oracle.Oracle.ray_for_pixel(ocam, x, y)
+            hit = next((e for e in P.o.intersect(ro[:3], rd[:3]) if e[0] >= 0.0), None)
+            if hit is not None:
+                out[y, x] = hit[1]
+    return out
+
+
+def adaptive_threshold(frame):
+    """A threshold for adaptive_mask that lists about half of the frame's pixels: the midpoint between two adjacent
+    distinct values of the per-pixel largest neighbour difference, the pair whose listed fraction is nearest 1/2 ->
+    (threshold, listed fraction); (None, 0.0) for a frame without two distinct values."""
+    import rray_amd as R
+
+    f = np.asarray(frame, np.float64)
+    H, W = f.shape[:2]
+    d = np.zeros((H, W))
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            ys, xs = slice(max(0, -dy), H - max(0, dy)), slice(max(0, -dx), W - max(0, dx))
+            yq, xq = slice(max(0, dy), H - max(0, -dy)), slice(max(0, dx), W - max(0, -dx))
+            d[ys, xs] = np.maximum(d[ys, xs], np.max(np.abs(f[ys, xs] - f[yq, xq]), axis=2))
+    vals = np.unique(d[np.isfinite(d)])
+    best = (None, 0.0)
+    for lo, hi in zip(vals[:-1], vals[1:]):
+        thr = float(0.5 * (lo + hi))
+        if not lo < thr < hi:
+            continue
+        frac = float(R.adaptive_mask(f, thr).mean())
+        if best[0] is None or abs(frac - 0.5) < abs(best[1] - 0.5):
+            best = (thr, frac)
+    return best
+
+
+def query_batch(P, spec, key):
+    """The seeded ray batch of the query mode, 1408 or 1472 rays of one scene:
+
+      a  the camera's 33 x 17 rays in a seeded shuffle (incoherent waves, invalid bundles)
+      b  the same rays in row-major order, direction lengths cycled through shape_rays.LENGTHS
+      c  secondary-like rays: over_point and reflectv of the oracle's hits of the camera rays in row-major order, the
+         first 30 or 94 of them (so that a + b + c is whole waves); fewer than 30 hits are filled up from a
+      d  four 64-ray fans, each the 8 x 8 tile of b with the most hits and an outlier in its first or its last lane: an
+         origin 1e5 scene sizes (|from - to|) away aimed at the scene, or the lane's own ray reversed (make_bundle takes
+         its centre and axis from the first and the last live lane)
+
+    A ray whose oracle intersection list holds a NaN t is replaced by the batch's first ray without one (the product
+    returns RR_E_NAN where the reference panics).  -> (origins (n, 3), directions (n, 3), number of replaced rays)."""
+    import oracle
+    import shape_rays as S
+
+    rng = np.random.default_rng(50_000 + key)
+    Hs, V = QUERY_SIZE
+    _, ocam = cameras(P, spec, Hs, V)
+    rays = [oracle.Oracle.ray_for_pixel(ocam, x, y) for y in range(V) for x in range(Hs)]
+    o = np.array([r[0][:3] for r in rays])
+    d = np.array([r[1][:3] for r in rays])
+    n = len(o)
+    perm = rng.permutation(n)
+    lens = np.array([S.LENGTHS[i % len(S.LENGTHS)] for i in range(n)])
+    bo, bd = o.copy(), d * lens[:, None]
+    co, cd = [], []
+    hit_px = np.zeros(n, bool)
+    for i in range(n):
+        xs = P.o.intersect(tuple(o[i]), tuple(d[i]))
+        if any(math.isnan(x[0]) for x in xs):
+            continue
+        hit = next((k for k, x in enumerate(xs) if x[0] >= 0.0), None)
+        if hit is not None:
+            hit_px[i] = True
+            c = P.o.prepare_computations(tuple(o[i]), tuple(d[i]), xs, hit)
+            co.append(c["over_point"][:3])
+            cd.append(c["reflectv"][:3])
+    n_c = 94 if len(co) >= 94 else 30
+    co, cd = co[:n_c], cd[:n_c]
+    for i in range(n_c - len(co)):
+        co.append(o[perm[i]].tolist())
+        cd.append(d[perm[i]].tolist())
+    frm, to = np.array(spec["from_"]), np.array(spec["to"])
+    size = float(np.linalg.norm(frm - to))
+    fo, fd = [], []
+    # the fans' tile: the full tile that holds the most hits (a fan of misses walks nothing; the first such tile in
+    # row-major order).  The four outlier variants share it: the same 63 rays, so a difference is the outlier's doing
+    hits2d = hit_px.reshape(V, Hs)
+    tx, ty = max(((tx, ty) for ty in range(V // 8) for tx in range(Hs // 8)),
+                 key=lambda t: int(hits2d[t[1] * 8:t[1] * 8 + 8, t[0] * 8:t[0] * 8 + 8].sum()))
+    idx = np.array([(ty * 8 + j) * Hs + tx * 8 + i for j in range(8) for i in range(8)])
+    for lane, far in ((0, True), (63, True), (0, False), (63, False)):
+        to_, td_ = bo[idx].copy(), bd[idx].copy()
+        if far:
+            to_[lane] = to + _unit(rng) * 1e5 * size
+            aim = to - to_[lane]
+            td_[lane] = aim / np.linalg.norm(aim)
+        else:
+            td_[lane] = -td_[lane]
+        fo.append(to_)
+        fd.append(td_)
+    O = np.concatenate([o[perm], bo, np.array(co).reshape(-1, 3)] + fo)
+    D = np.concatenate([d[perm], bd, np.array(cd).reshape(-1, 3)] + fd)
+    assert (len(O) - 256) % 64 == 0
+    nan = [any(math.isnan(x[0]) for x in P.o.intersect(tuple(a), tuple(b))) for a, b in zip(O, D)]
+    good = nan.index(False)
+    for i, bad in enumerate(nan):
+        if bad:
+            O[i], D[i] = O[good], D[good]
+    return np.ascontiguousarray(O), np.ascontiguousarray(D), int(sum(nan))
+
+
+def shadow_pairs(P, spec, key, over_points):
+    """(points, lights) for is_shadowed: every given over_point with a light that cycles per lane through the scene's
+    light positions (an area light's centre), the camera's position and two seeded points inside the bounds of the
+    finite over_points."""
+    rng = np.random.default_rng(60_000 + key)
+    p = np.asarray(over_points, np.float64).reshape(-1, 3)
+    lights = [P.b.light[15 * i:15 * i + 3] for i in range(len(P.b.light_kind))] + [list(spec["from_"])]
+    fin = p[np.isfinite(p).all(axis=1)]
+    lo, hi = (fin.min(axis=0), fin.max(axis=0)) if len(fin) else (np.zeros(3), np.ones(3))
+    lights += [(lo + rng.random(3) * (hi - lo)).tolist() for _ in range(2)]
+    return p, np.array([lights[i % len(lights)] for i in range(len(p))], np.float64)

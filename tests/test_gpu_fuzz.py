@@ -41,27 +41,9 @@ def test_fuzz_scene_bit_exact(renderer, seed):
     cam, ocam = F.cameras(P, spec, W * aa, H * aa)
     renderer.upload(P.b)
     got = renderer.render(cam, aa=aa, max_depth=depth, canvas=True)
-    canvas, st = P.o.render(ocam, max_depth=depth)  # libm pow: the reference's own arithmetic
-    P.o.set_pow_mode(1)
-    canvas_cr, st_cr = P.o.render(ocam, max_depth=depth)  # correctly rounded x^n
-    P.o.set_pow_mode(0)
-    diff = np.argwhere((got["canvas"] != canvas_cr).any(axis=2))
-    pow_only = np.argwhere((got["canvas"] != canvas).any(axis=2))
-    oracles_differ = (canvas != canvas_cr).any(axis=2)
-    counts = {k: (got["stats"][k], v) for k, v in (("rays", st["rays"] - st["shadow_rays"]),
-                                                    ("shadow_rays", st["shadow_rays"]),
-                                                    ("shade_events", st["shade_events"]))}
-    ok = len(diff) == 0 and all(a == b for a, b in counts.values()) and st == st_cr
-    ok = ok and all(oracles_differ[y, x] for y, x in pow_only)
-    if not ok:
-        print(f"seed {seed} ({cat}) {W}x{H} aa{aa}: {len(diff)} samples differ from the correctly rounded "
-              f"oracle, {len(pow_only)} from the libm one; counts (gpu, oracle) {counts}")
-        for y, x in diff[:10]:
-            print(f"  sample ({x},{y}): gpu {got['canvas'][y, x].tolist()} oracle {canvas_cr[y, x].tolist()}")
-        print("\n".join(P.log))
-    elif len(pow_only):
-        print(f"seed {seed} ({cat}): {len(pow_only)} samples differ from libm pow by its rounding only")
-    assert ok, f"seed {seed} ({cat})"
+    # libm pow (the reference's own arithmetic) and correctly rounded x^n
+    canvas_cr, st_cr, (canvas, st) = F.oracle_frame(P, ocam, depth, libm=True)
+    F.check_frame(got, P, f"seed {seed} ({cat}) {W}x{H} aa{aa}", canvas_cr, st_cr, libm=(canvas, st))
     assert float(np.max(np.abs(got["avg"] - P.o.aa_average(canvas, aa)))) <= 1e-12
 
 
@@ -82,25 +64,9 @@ def test_general_fuzz_bit_exact(renderer, seed):
     cam, ocam = F.cameras(P, spec, W * aa, H * aa)
     renderer.upload(P.b)
     got = renderer.render(cam, aa=aa, max_depth=depth, canvas=True)
-    canvas, st = P.o.render(ocam, max_depth=depth)  # libm pow: the reference's own arithmetic
-    P.o.set_pow_mode(1)
-    canvas_cr, st_cr = P.o.render(ocam, max_depth=depth)  # correctly rounded x^n
-    P.o.set_pow_mode(0)
-    diff = np.argwhere((got["canvas"] != canvas_cr).any(axis=2))
-    pow_only = np.argwhere((got["canvas"] != canvas).any(axis=2))
-    oracles_differ = (canvas != canvas_cr).any(axis=2)
-    counts = {k: (got["stats"][k], v) for k, v in (("rays", st["rays"] - st["shadow_rays"]),
-                                                    ("shadow_rays", st["shadow_rays"]),
-                                                    ("shade_events", st["shade_events"]))}
-    ok = len(diff) == 0 and all(a == b for a, b in counts.values()) and st == st_cr
-    ok = ok and all(oracles_differ[y, x] for y, x in pow_only)
-    if not ok:
-        print(f"seed {seed} ({cat}) {W}x{H} aa{aa}: {len(diff)} samples differ from the correctly rounded "
-              f"oracle, {len(pow_only)} from the libm one; counts (gpu, oracle) {counts}")
-        for y, x in diff[:10]:
-            print(f"  sample ({x},{y}): gpu {got['canvas'][y, x].tolist()} oracle {canvas_cr[y, x].tolist()}")
-        print("\n".join(P.log))
-    assert ok, f"seed {seed} ({cat})"
+    # libm pow (the reference's own arithmetic) and correctly rounded x^n
+    canvas_cr, st_cr, (canvas, st) = F.oracle_frame(P, ocam, depth, libm=True)
+    F.check_frame(got, P, f"seed {seed} ({cat}) {W}x{H} aa{aa}", canvas_cr, st_cr, libm=(canvas, st))
     assert float(np.max(np.abs(got["avg"] - P.o.aa_average(canvas, aa)))) <= 1e-12
 
 
@@ -115,20 +81,8 @@ def test_area_light_fuzz_bit_exact(renderer, seed):
     cam, ocam = F.cameras(P, spec, W * aa, H * aa)
     renderer.upload(P.b)
     got = renderer.render(cam, aa=aa, max_depth=depth, seed=seed, canvas=True)
-    P.o.set_pow_mode(1)
-    canvas_cr, st = P.o.render(ocam, max_depth=depth, seed=seed)
-    P.o.set_pow_mode(0)
-    diff = np.argwhere((got["canvas"] != canvas_cr).any(axis=2))
-    counts = {k: (got["stats"][k], v) for k, v in (("rays", st["rays"] - st["shadow_rays"]),
-                                                    ("shadow_rays", st["shadow_rays"]),
-                                                    ("shade_events", st["shade_events"]))}
-    ok = len(diff) == 0 and all(a == b for a, b in counts.values())
-    if not ok:
-        print(f"seed {seed} ({cat}) {W}x{H} aa{aa}: {len(diff)} samples differ; counts (gpu, oracle) {counts}")
-        for y, x in diff[:10]:
-            print(f"  sample ({x},{y}): gpu {got['canvas'][y, x].tolist()} oracle {canvas_cr[y, x].tolist()}")
-        print("\n".join(P.log))
-    assert ok, f"seed {seed} ({cat})"
+    canvas_cr, st = F.oracle_frame(P, ocam, depth, seed)
+    F.check_frame(got, P, f"seed {seed} ({cat}) {W}x{H} aa{aa}", canvas_cr, st)
 
 
 @pytest.mark.parametrize("seed", range(48))
@@ -144,17 +98,5 @@ def test_own_skip_fuzz_bit_exact(renderer, seed):
     cam, ocam = F.cameras(P, spec, W * aa, H * aa)
     renderer.upload(P.b)
     got = renderer.render(cam, aa=aa, max_depth=depth, seed=seed, canvas=True)
-    P.o.set_pow_mode(1)
-    canvas_cr, st = P.o.render(ocam, max_depth=depth, seed=seed)
-    P.o.set_pow_mode(0)
-    diff = np.argwhere((got["canvas"] != canvas_cr).any(axis=2))
-    counts = {k: (got["stats"][k], v) for k, v in (("rays", st["rays"] - st["shadow_rays"]),
-                                                    ("shadow_rays", st["shadow_rays"]),
-                                                    ("shade_events", st["shade_events"]))}
-    ok = len(diff) == 0 and all(a == b for a, b in counts.values())
-    if not ok:
-        print(f"seed {seed} ({cat}) {W}x{H} aa{aa}: {len(diff)} samples differ; counts (gpu, oracle) {counts}")
-        for y, x in diff[:10]:
-            print(f"  sample ({x},{y}): gpu {got['canvas'][y, x].tolist()} oracle {canvas_cr[y, x].tolist()}")
-        print("\n".join(P.log))
-    assert ok, f"seed {seed} ({cat})"
+    canvas_cr, st = F.oracle_frame(P, ocam, depth, seed)
+    F.check_frame(got, P, f"seed {seed} ({cat}) {W}x{H} aa{aa}", canvas_cr, st)
