@@ -8,11 +8,15 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <string_view>
 #include <vector>
+
+#include <unistd.h>
 
 #include "../../include/rray/rray.h"
 #include "device_guard.hpp"
 #include "flatten.hpp"
+#include "frame_plan.hpp"
 #include "kernels.hpp"
 #include "multi.hpp"
 #include "partition.hpp"
@@ -189,8 +193,26 @@ rr::DevCamera dev_camera(const rr_camera* c) {
     return d;
 }
 
-// Runs the wavefront levels for `total` level-0 events; level-0 rays come from the camera or from
-// ctx->rays0 (color_at).  Results (color_at values) land in `out` (3 doubles per event).
+// the level-0 arguments a camera frame starts from: the camera, the part layout and the jitter
+void set_camera(rr::LevelArgs& A, const rr_camera* cam) {
+    A.cam = dev_camera(cam);
+    A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
+                   A.cam.origin[3] == 1.0;
+}
+rr::LevelArgs camera_args(const rr_camera* cam, const rr_render_opts* o, int32_t aa, int32_t part, int32_t block) {
+    rr::LevelArgs A{};
+    set_camera(A, cam);
+    A.hs = cam->hsize;
+    A.aa = aa;
+    A.part = part;
+    A.nparts = o->nparts;
+    A.block_rows = block;
+    A.rays0 = nullptr;
+    A.seed = o->seed;
+    A.jitter_mode = o->jitter_mode;
+    return A;
+}
+
 // The context's workspace is used on one stream at a time: a call on another stream than the
 // previous one first waits for it (one event, only when the stream changes).
 hipError_t claim_stream(rr_ctx* c, hipStream_t st) {
@@ -261,54 +283,12 @@ uint32_t persist_heads() {
     return h;
 }
 
-// Worst-case queue bytes of a batch of nb level-0 events: every shading event queues max_children
-// children (k), so level d holds at most nb * k^d events.  The levels are launched for that capacity
-// and read their live counts from HBM (no host round trip between levels).
-struct LevelPlan {
-    int64_t cap[RR_MAX_DEPTH + 1];  // capacity per level (array size; segmented: nseg * seg_cap)
-    int64_t seg_cap[RR_MAX_DEPTH + 1];  // segmented (fused) levels >= 1: capacity of each of RR_NSEG segments
-    int levels;                     // levels launched (depth + 1, or 1 without secondary rays)
-    int64_t ev_cap[2];              // ev_a (odd levels), ev_b (even levels >= 2)
-    int64_t max_cap;
-    size_t bytes;
-};
-// fused: levels >= 1 in RR_NSEG segments (wavefront.hpp); level 0's block b fills segment b % RR_NSEG
-// of level 1, so a segment holds at most ceil(blocks / RR_NSEG) * 256 * k events, and a segment of
-// level d feeds only the same segment of level d + 1
-LevelPlan plan_levels(int64_t nb, int k, int max_depth, bool ext, bool fused = false) {
-    LevelPlan p{};
-    int64_t w = nb;
-    for (int d = 0; d <= max_depth; ++d) {
-        p.cap[d] = w;
-        p.levels = d + 1;
-        p.max_cap = std::max(p.max_cap, w);
-        const bool kids = d < max_depth && k > 0;
-        if (!kids) break;
-        p.bytes += (size_t)w * (sizeof(rr::CombRec) + (ext ? sizeof(rr::CombExt) : 0) + sizeof(int32_t));
-        if (fused) {
-            p.seg_cap[d + 1] = d == 0 ? (((nb + 255) / 256 + rr::RR_NSEG - 1) / rr::RR_NSEG) * 256 * k : p.seg_cap[d] * k;
-            p.seg_cap[d + 1] = (p.seg_cap[d + 1] + 255) / 256 * 256;
-            w = rr::RR_NSEG * p.seg_cap[d + 1];
-        } else {
-            w *= k;
-        }
-        int64_t& e = p.ev_cap[d % 2];  // level d+1 lands in ev_a when d is even
-        e = std::max(e, w);
-    }
-    p.bytes += (size_t)p.max_cap * (sizeof(rr::HitRec) + 2 * sizeof(double) + sizeof(int32_t));
-    p.bytes += (size_t)(p.ev_cap[0] + p.ev_cap[1]) * sizeof(rr::Event);
-    return p;
-}
-
-// pixel waves of a part (A.pw): bands of two output rows, pw_wpb waves each
-int64_t pixel_waves(const rr::LevelArgs& A) { return (int64_t)((A.pw_rows + 1) / 2) * A.pw_wpb; }
-
 // level-0 index math: magic divisors, and the wave-uniform tile path when every tile is a full 8x8 and the
 // batch starts on a tile boundary
 void set_level0_index(rr::LevelArgs& A) {
     A.aa_magic = A.aa > 1 ? (uint32_t)((1ull << 32) / (uint64_t)A.aa) : 0u;
     A.br_magic = A.block_rows > 1 ? (uint32_t)((1ull << 32) / (uint64_t)A.block_rows) : 0u;
-    A.tile_fast = !A.rays0 && A.lrows > 0 && A.hs % 8 == 0 && A.lrows % 8 == 0 && A.base % 64 == 0 ? 1 : 0;
+    A.tile_fast = rr::full_tiles(A.rays0 != nullptr, A.hs, A.lrows, A.base) ? 1 : 0;
     A.tiles_per_row = (uint32_t)(A.hs / 8);
 }
 
@@ -325,7 +305,7 @@ int tile_bundles(rr_ctx* c, const rr::LevelArgs& base_args, hipStream_t st, cons
     // few-node flat scenes with LDS culls walk node by node without bundles (walk_nodes)
     if (!c->S.has_groups && !c->S.general && c->S.lds_culls && c->S.n_nodes <= rr::RR_BUNDLE_MIN_NODES) return RR_OK;
     // one bundle per 8x8 tile, or per pixel wave (A.pw)
-    const int64_t n_tiles = T.pw ? pixel_waves(T) : T.hs * T.lrows / 64;
+    const int64_t n_tiles = T.pw ? rr::pixel_waves(T.pw_rows, T.pw_wpb) : T.hs * T.lrows / 64;
     const size_t want = (size_t)n_tiles * rr::RR_TILE_BUNDLE_FLOATS * sizeof(float);
     if (want > c->tiles.bytes) {
         HIPCHK(c->tiles.ensure(want));
@@ -352,17 +332,55 @@ int tile_bundles(rr_ctx* c, const rr::LevelArgs& base_args, hipStream_t st, cons
     return RR_OK;
 }
 
-// The averaged image can be written by the level-0 waves themselves (deliver_wave_avg) when every
-// pixel's samples lie in one wave's 8x8 tile (aa in {2, 4, 8}, full tiles: the tile_fast layout) and no
-// sample spawns a secondary ray (fused levels with no reflective / transparent material, or depth 0).
-bool wave_avg_ok(const rr_ctx* c, int32_t aa, int64_t hs, int64_t local_rows, int max_depth) {
-    // (reflection chains run inside the level-0 wave, chain_levels: every sample is final in its wave too)
-    // (and the color_at trees of transparent scenes, tree_levels, likewise)
-    return (aa == 2 || aa == 4 || aa == 8) && hs % 8 == 0 && local_rows % 8 == 0 && local_rows > 0 &&
-           ((rr::fused_levels(c->S) &&
-             (c->host.max_children == 0 || max_depth == 0 || rr::chain_levels(c->S, c->host.max_children, max_depth))) ||
-            rr::tree_levels(c->S));
+// What a call's plans (frame_plan.hpp) read of the scene and the environment, gathered once per ABI call and never
+// kept: the tests flip the switches between renders on one context.  The family predicates are the device units'
+// own answers (each switch of theirs keeps its one reader) for the depth the call renders at.
+struct FrameFacts {
+    rr::FrameTraits traits;
+    rr::FrameSwitches sw;
+};
+static_assert(rr::kOrderGroup == rr::RR_ORDER_GROUP, "frame_plan.hpp's order group is the sort's");
+// api.cpp's own switches in one pass over the environment, which costs what one getenv does (six of them per
+// frame would show in the sub-millisecond frames)
+rr::FrameSwitches read_switches() {
+    rr::FrameSwitches s;
+    for (char** e = environ; e && *e; ++e) {
+        if (std::strncmp(*e, "RRAY_", 5) != 0) continue;
+        const char* name = *e + 5;
+        const char* eq = std::strchr(name, '=');
+        if (!eq) continue;
+        const std::string_view key(name, (size_t)(eq - name));
+        if (key == "AA_PASSES")
+            s.aa_passes = std::max(1, std::atoi(eq + 1));
+        else if (key == "DEEP")
+            s.deep = std::atoi(eq + 1) == 1;
+        else if (key == "ORDER_GROUP")
+            s.order_group = std::atoi(eq + 1) == rr::kOrderGroup ? rr::kOrderGroup : 1;
+        else if (key == "NO_CHAIN_ORDER")
+            s.no_chain_order = true;
+        else if (key == "NO_TILE_GUESS")
+            s.no_tile_guess = true;
+        else if (key == "NO_PW")
+            s.no_pw = true;
+    }
+    return s;
 }
+FrameFacts frame_facts(const rr_ctx* c, int max_depth) {
+    const rr::DevScene& S = c->S;
+    FrameFacts f;
+    f.traits.has_groups = S.has_groups;
+    f.traits.general = S.general;
+    f.traits.has_area = S.has_area;
+    f.traits.has_transparent = c->host.has_transparent;
+    f.traits.max_children = c->host.max_children;
+    f.traits.fused = rr::fused_levels(S);
+    f.traits.chain = rr::chain_levels(S, c->host.max_children, max_depth);
+    f.traits.tree = rr::tree_levels(S);
+    f.sw = read_switches();
+    return f;
+}
+
+rr::KernelProf* kprof(rr_ctx* c) { return c->profile ? &c->prof : nullptr; }
 
 // The box average of a canvas-path frame (aa outside the in-wave cases, e.g. C3's aa = 3) overlapped with the
 // render: the frame runs in passes of whole output rows, and each pass's rows are averaged on the context's
@@ -373,301 +391,310 @@ struct AaPasses {
     int64_t width;  // output pixels per row
     int32_t aa;
 };
+// `rows` output rows from row y0 on, from their samples at src
+hipError_t launch_average(const AaPasses& a, const double* src, int64_t y0, int64_t rows, hipStream_t st,
+                          rr::KernelProf* kp) {
+    return a.f32 ? rr::launch_aa_f32(src, static_cast<float*>(a.avg) + 3 * y0 * a.width, a.width, rows, a.aa, st, kp)
+                 : rr::launch_aa(src, static_cast<double*>(a.avg) + 3 * y0 * a.width, a.width, rows, a.aa, st, kp);
+}
 
-int run_levels(rr_ctx* c, const rr::LevelArgs& base_args, int64_t total, int max_depth, double* out, hipStream_t st,
-               void* avg = nullptr, int32_t avg_f32 = 0, int32_t aa_wave = 0, const AaPasses* aap = nullptr) {
-    const bool ext = c->host.has_transparent != 0;
-    const bool fused = rr::fused_levels(c->S);
-    // reflection chains inside the level-0 waves (chain_kernel), or the color_at trees of transparent scenes
-    // (tree_kernel): one level, no recursion queues
-    const bool tree = rr::tree_levels(c->S);
-    const bool chain = tree || rr::chain_levels(c->S, c->host.max_children, max_depth);
-    const int k = chain ? 0 : c->host.max_children;
-    const int plan_depth = chain ? 0 : max_depth;
-    // batch: at most c->batch camera samples, shrunk (power-of-two steps, tile-aligned) until the
-    // worst-case queues fit the context's budget and every event index fits in int32
-    int64_t B = std::max<int64_t>(64, std::min<int64_t>(c->batch, total));
-    for (;;) {
-        const LevelPlan p = plan_levels(B, k, plan_depth, ext, fused);
-        const int64_t last = p.cap[p.levels - 1];
-        if (B <= 4096 || (p.bytes <= c->queue_budget && last < ((int64_t)1 << 31) && p.max_cap < ((int64_t)1 << 31)))
-            break;
-        B = std::max<int64_t>(4096, (B / 2) & ~(int64_t)63);
-    }
-    // AA passes: batches of whole output rows (a multiple of lcm(8, aa) sample rows, so every batch is whole
-    // 8-row tile bands and whole pixels), about kRR_AA_PASSES of them
-    bool passes = false;
-    if (aap && out && !base_args.rays0 && base_args.hs % 8 == 0 && base_args.lrows % 8 == 0) {
-        int64_t rows_unit = 8;
-        while (rows_unit % aap->aa) rows_unit += 8;
-        const int64_t unit = rows_unit * base_args.hs;
-        const int64_t units = total / unit;
-        // default one pass: measured on C3 (chain kernel), 2 / 4 / 8 passes cost 7.29 / 7.61 / 8.01 ms per frame
-        // against 7.08 — each pass ends in its own tail of long chains, and the averages did not overlap it
-        const int np = std::max(1, std::atoi(std::getenv("RRAY_AA_PASSES") ? std::getenv("RRAY_AA_PASSES") : "1"));
-        if (total % unit == 0 && units >= 2 && np > 1 && B >= unit) {
-            const int64_t per = std::min((units + np - 1) / np, B / unit);
-            B = per * unit;
-            passes = true;
-            if (!c->aa_stream) HIPCHK(hipStreamCreateWithFlags(&c->aa_stream, hipStreamNonBlocking));
-        }
-    }
-    // listed pixels (adaptive frames' refine pass): one batch, served by the in-wave kernels only
-    const bool listed = base_args.list != nullptr;
-    if (listed && (B < total || !(tree || chain || (fused && (k == 0 || max_depth == 0)))))
-        return fail(RR_E_ARG, "internal: the listed-pixel pass needs one batch of a production kernel family");
-    const LevelPlan P = plan_levels(B, k, plan_depth, ext, fused);
-    if (P.max_cap >= ((int64_t)1 << 31)) return fail(RR_E_LIMIT, "recursion queues exceed 2^31 events (lower max_depth)");
+// where a run's results go (run_levels' arguments)
+struct FrameOut {
+    double* out;
+    void* avg;
+    int32_t avg_f32, aa_wave;
+    const AaPasses* aap;
+};
+
+rr::FramePlan plan_run(const rr_ctx* c, const FrameFacts& facts, const rr::LevelArgs& A, int64_t total, int max_depth,
+                       const FrameOut& o) {
+    rr::FrameRequest r{};
+    r.total = total;
+    r.max_depth = max_depth;
+    r.hs = A.hs;
+    r.lrows = A.lrows;
+    r.aa = A.aa;
+    r.block_rows = A.block_rows;
+    r.rays0 = A.rays0 != nullptr;
+    r.listed = A.list != nullptr;
+    r.pw = A.pw != 0;
+    r.pw_rows = A.pw_rows;
+    r.pw_wpb = A.pw_wpb;
+    r.canvas = o.out != nullptr;
+    r.box_avg = o.aap != nullptr;
+    r.aa_wave = o.aa_wave;
+    r.batch = c->batch;
+    r.queue_budget = c->queue_budget;
+    r.zero_next = c->zero_next;
+    return rr::plan_frame(facts.traits, facts.sw, r);
+}
+
+int grow_workspace(rr_ctx* c, const rr::FramePlan& plan) {
+    const rr::LevelPlan& P = plan.P;
     if ((int)c->comb.size() < P.levels) {
         c->comb.resize(P.levels);
         c->comb_ext.resize(P.levels);
         c->pend.resize(P.levels);
     }
-    if (!fused && !tree) {  // hit records and n1/n2 lists: the unfused trace / n1n2 / shade kernels only
+    if (plan.family == rr::Family::Unfused) {  // hit records and n1/n2 lists: the trace / n1n2 / shade kernels only
         HIPCHK(c->hit.ensure(P.max_cap * sizeof(rr::HitRec)));
         HIPCHK(c->n12.ensure(P.max_cap * 2 * sizeof(double)));
         HIPCHK(c->n1n2.ensure(P.max_cap * sizeof(int32_t)));
     }
     for (int d = 0; d + 1 < P.levels; ++d) {
         HIPCHK(c->comb[d].ensure(P.cap[d] * sizeof(rr::CombRec)));
-        if (ext) HIPCHK(c->comb_ext[d].ensure(P.cap[d] * sizeof(rr::CombExt)));
+        if (plan.ext) HIPCHK(c->comb_ext[d].ensure(P.cap[d] * sizeof(rr::CombExt)));
         HIPCHK(c->pend[d].ensure(P.cap[d] * sizeof(int32_t)));
     }
     if (P.ev_cap[0]) HIPCHK(c->ev_a.ensure(P.ev_cap[0] * sizeof(rr::Event)));
     if (P.ev_cap[1]) HIPCHK(c->ev_b.ensure(P.ev_cap[1] * sizeof(rr::Event)));
-    unsigned int* lc = c->lcount.as<unsigned int>();
-    // deep chains (chain_kernel DEEP): frames whose samples are delivered one by one (not the in-wave AA average)
-    // can send the chains still reflecting at depth RR_DEEP_FROM to a packed, segmented queue for a second launch.
-    // Opt-in (RRAY_DEEP=1): on C3 the deep launch took 1.85 ms for what the camera waves did in 1.54 — the deep
-    // rays' walks are latency-bound whether their waves are full or not
-    const bool spill = chain && !tree && aa_wave == 0 && !base_args.pw && !base_args.list &&max_depth >= rr::RR_DEEP_FROM && std::getenv("RRAY_DEEP") &&
-                       std::atoi(std::getenv("RRAY_DEEP")) == 1;
-    const int64_t deep_seg_cap = (int64_t)256 << rr::RR_DEEP_SHIFT;
-    const int64_t deep_nseg = (((B + 255) / 256) + (1 << rr::RR_DEEP_SHIFT) - 1) >> rr::RR_DEEP_SHIFT;
-    if (spill) HIPCHK(c->deep.ensure((size_t)deep_nseg * deep_seg_cap * sizeof(rr::DeepRec)));
-    if (spill && (size_t)(deep_nseg + 2) * sizeof(unsigned int) > c->deep_count.bytes)
-        HIPCHK(c->deep_count.ensure((size_t)(deep_nseg + 2) * sizeof(unsigned int)));
-    // cost-ordered level-0 tiles: one-batch fused frames of full 8x8 tiles whose level 0 is the whole frame (no
-    // secondary rays) in scenes with groups, where tile costs spread widest (mesh silhouettes against floor:
-    // C4 0.596 -> 0.511 ms per frame).  Flat scenes' tiles cost alike (C2 +0.6 % with the order), and frames
-    // with reflections lose their children queues' tile order (C3 +2 %): both keep launch order.
-    rr::LevelArgs T0 = base_args;
-    T0.base = 0;
-    set_level0_index(T0);
-    // chain frames order their camera waves too (tiles or pixel waves; the chains' depths spread tile costs widely)
-    const int64_t n_tiles = T0.pw ? pixel_waves(T0) : T0.tile_fast ? T0.hs * T0.lrows / 64 : 0;
-    // the order's unit: single waves, so a block's four waves cost alike (the costliest first) and the block's
-    // resources free together.  Groups of a block's four adjacent tiles (RRAY_ORDER_GROUP=4: their output rows join
-    // into whole cache lines) measured slower: C3 6.33 vs 7.17 ms, C4 0.510 vs 0.520 ms, C5 equal
-    int order_group = 1;
-    if (const char* g = std::getenv("RRAY_ORDER_GROUP")) order_group = std::atoi(g) == rr::RR_ORDER_GROUP ? rr::RR_ORDER_GROUP : 1;
-    const bool order_ok = (fused || tree) && !c->S.general && B >= total && n_tiles > 0 && n_tiles < ((int64_t)1 << 31) &&
-                          (order_group == 1 || n_tiles % 4 == 0) &&  // the group order permutes a block's four tiles
-                          (T0.pw || n_tiles * 64 == total) &&
-                          ((c->S.has_groups && (k == 0 || max_depth == 0)) || (chain && !std::getenv("RRAY_NO_CHAIN_ORDER")));
-    // the launch's last block may hold up to three wave slots past the last tile (n_tiles not a multiple of 4: a
-    // pixel-wave part of 270 output rows has 148 230 waves): the order and cost arrays run to whole blocks, the extra
-    // slots' order entries are their own indices (their lanes are past the launch's samples and do nothing but record
-    // a cost nobody sorts).  Until round 6 such layouts ran unordered: C3's 8-part rows among them.
-    const int64_t n_pad = (n_tiles + 3) & ~(int64_t)3;
-    if (order_ok) {
-        HIPCHK(c->tile_cost.ensure((size_t)n_pad * sizeof(uint32_t)));
-        HIPCHK(c->tile_perm.ensure((size_t)n_pad * sizeof(uint32_t)));
+    if (plan.passes && !c->aa_stream) HIPCHK(hipStreamCreateWithFlags(&c->aa_stream, hipStreamNonBlocking));
+    if (plan.spill) {
+        HIPCHK(c->deep.ensure((size_t)plan.deep_nseg * plan.deep_seg_cap * sizeof(rr::DeepRec)));
+        HIPCHK(c->deep_count.ensure((size_t)(plan.deep_nseg + 2) * sizeof(unsigned int)));
+    }
+    if (plan.order.ok) {
+        HIPCHK(c->tile_cost.ensure((size_t)plan.order.n_pad * sizeof(uint32_t)));
+        HIPCHK(c->tile_perm.ensure((size_t)plan.order.n_pad * sizeof(uint32_t)));
         HIPCHK(c->tile_hist.ensure(256 * sizeof(uint32_t)));
-        rr_ctx::TileKey key{};  // the layout only: a camera change keeps the order (costs stay a good guess)
-        key.hs = T0.hs;
-        key.lrows = T0.lrows;
-        key.aa = T0.aa;
-        key.part = T0.part;
-        key.nparts = T0.nparts;
-        key.block_rows = T0.block_rows;
-        key.pw = T0.pw;
-        key.pad = (chain ? 1 : 0) | (order_group == 1 ? 2 : 0);  // chain and level-0-only frames of one layout, and
-                                                                  // each order unit, keep orders of their own
-        if (c->order_tiles != n_tiles || std::memcmp(&key, &c->order_key, sizeof key) != 0) {
-            c->order_valid = false;
-            c->order_tiles = n_tiles;
-            c->order_key = key;
-            if (n_pad > n_tiles) {  // the identity for the slots past the last tile
-                for (int64_t t = n_tiles; t < n_pad; ++t) c->perm_tail[t - n_tiles] = (uint32_t)t;
-                HIPCHK(hipMemcpyAsync(c->tile_perm.as<uint32_t>() + n_tiles, c->perm_tail,
-                                      (size_t)(n_pad - n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            }
-        }
-        // a layout's first frame: order by a guess from the camera bundles (launch order left the first frame's
-        // slowest tiles last: C4 0.59 vs 0.51 ms), and re-sort by the measured costs right after it
-        if (!c->order_valid && T0.tile_bundles && !std::getenv("RRAY_NO_TILE_GUESS")) {
-            HIPCHK(rr::launch_tile_guess(c->S, T0.tile_bundles, c->tile_cost.as<uint32_t>(), n_tiles, st));
-            HIPCHK(rr::launch_tile_order(c->tile_cost.as<uint32_t>(), c->tile_perm.as<uint32_t>(),
-                                         c->tile_hist.as<uint32_t>(), n_tiles, order_group, st));
-            c->order_valid = true;
-            c->order_age = kRR_ORDER_EVERY - 1;
+    }
+    return RR_OK;
+}
+
+// ---- the level-0 cost order of frames with plan.order.ok: the three functions below are all that touches the
+// context's order state (order_valid / order_age / order_key / order_tiles / perm_tail) ----
+int sort_order(rr_ctx* c, const rr::FramePlan& plan, hipStream_t st) {
+    HIPCHK(rr::launch_tile_order(c->tile_cost.as<uint32_t>(), c->tile_perm.as<uint32_t>(), c->tile_hist.as<uint32_t>(),
+                                 plan.order.n_tiles, plan.order.group, st));
+    c->order_valid = true;
+    return RR_OK;
+}
+// before the frame's launches: a new layout drops the order, and a layout's first frame is ordered by a guess
+int refresh_order(rr_ctx* c, const rr::LevelArgs& base_args, const rr::FramePlan& plan, bool guess, hipStream_t st) {
+    const int64_t n_tiles = plan.order.n_tiles, n_pad = plan.order.n_pad;
+    rr_ctx::TileKey key{};  // the layout only: a camera change keeps the order (costs stay a good guess)
+    key.hs = base_args.hs;
+    key.lrows = base_args.lrows;
+    key.aa = base_args.aa;
+    key.part = base_args.part;
+    key.nparts = base_args.nparts;
+    key.block_rows = base_args.block_rows;
+    key.pw = base_args.pw;
+    key.pad = plan.order.pad;
+    if (c->order_tiles != n_tiles || std::memcmp(&key, &c->order_key, sizeof key) != 0) {
+        c->order_valid = false;
+        c->order_tiles = n_tiles;
+        c->order_key = key;
+        if (n_pad > n_tiles) {  // the identity for the slots past the last tile
+            for (int64_t t = n_tiles; t < n_pad; ++t) c->perm_tail[t - n_tiles] = (uint32_t)t;
+            HIPCHK(hipMemcpyAsync(c->tile_perm.as<uint32_t>() + n_tiles, c->perm_tail,
+                                  (size_t)(n_pad - n_tiles) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
     }
-    for (int64_t base = 0; base < total; base += B) {
-        const int64_t nb = std::min(B, total - base);
-        const LevelPlan p = plan_levels(nb, k, plan_depth, ext, fused);
-        // per-level queue counters [level][LC_*], zeroed once per batch (appends, pending, n1/n2 lists)
-        // (the in-wave chains and trees use none: no memset in their frames, which cost a C1 frame 9.6 us as two fills)
-        if (p.levels > 1 || (ext && !tree))
-            HIPCHK(hipMemsetAsync(lc, 0, (size_t)p.levels * rr::LC_COUNT * sizeof(unsigned int), st));
-        if (spill) HIPCHK(hipMemsetAsync(c->deep_count.p, 0, (size_t)deep_nseg * sizeof(unsigned int), st));
+    // a layout's first frame: order by a guess from the camera bundles (launch order left the first frame's
+    // slowest tiles last: C4 0.59 vs 0.51 ms), and re-sort by the measured costs right after it
+    if (!c->order_valid && base_args.tile_bundles && guess) {
+        HIPCHK(rr::launch_tile_guess(c->S, base_args.tile_bundles, c->tile_cost.as<uint32_t>(), n_tiles, st));
+        int rc = sort_order(c, plan, st);
+        if (rc != RR_OK) return rc;
+        c->order_age = kRR_ORDER_EVERY - 1;
+    }
+    return RR_OK;
+}
+// level 0's arguments.  The waves record their costs only in a frame the sort after it reads (every
+// kRR_ORDER_EVERY-th): each record is one scattered 4-byte store per wave, a partial line that L2 writes back alone
+// (47 MB of the C3 chain kernel's 0.55 GB of writes per frame, profiles/r05/attrib_c3.txt)
+void order_level0_args(const rr_ctx* c, const rr::FramePlan& plan, rr::LevelArgs& A) {
+    const bool sort_after = !c->order_valid || c->order_age + 1 >= kRR_ORDER_EVERY;
+    A.tile_perm = c->order_valid ? c->tile_perm.as<uint32_t>() : nullptr;
+    A.tile_cost = sort_after ? c->tile_cost.as<uint32_t>() : nullptr;
+    A.order_group = plan.order.group;
+}
+// after level 0's launch: one frame older, re-sorted by the costs it recorded when due
+int age_order(rr_ctx* c, const rr::FramePlan& plan, hipStream_t st) {
+    if (c->order_valid && ++c->order_age < kRR_ORDER_EVERY) return RR_OK;
+    int rc = sort_order(c, plan, st);
+    if (rc == RR_OK) c->order_age = 0;
+    return rc;
+}
+
+// Level d of the batch at `base` (p: the batch's queues): the frame's arguments plus the level's queues, outputs,
+// counters and, at level 0 of ordered frames, the order.
+rr::LevelArgs level_args(rr_ctx* c, const rr::LevelArgs& base_args, const rr::FramePlan& plan, const rr::LevelPlan& p,
+                         int64_t base, int d, int max_depth, const FrameOut& o) {
+    unsigned int* lc = c->lcount.as<unsigned int>();  // per-level queue counters [level][LC_*]
+    const bool fused = plan.fused, ext = plan.ext, children_possible = d + 1 < p.levels;
+    rr::LevelArgs A = base_args;
+    A.base = base;
+    set_level0_index(A);
+    A.level = d;
+    A.rem = max_depth - d;
+    A.n = A.pw ? plan.pw_n : p.cap[d];  // pixel waves: whole waves of 7 pixels
+    A.n_dev = d > 0 ? lc + (d - 1) * rr::LC_COUNT + rr::LC_CHILDREN : base_args.list ? base_args.n_dev : nullptr;
+    A.nseg = fused && d > 0 ? rr::RR_NSEG : 1;
+    A.nseg_out = fused ? rr::RR_NSEG : 1;
+    A.seg_cap = fused && d > 0 ? p.seg_cap[d] : 0;
+    A.seg_cap_out = fused && children_possible ? p.seg_cap[d + 1] : 0;
+    A.seg_count = lc + d * rr::LC_COUNT + rr::LC_SEG0;
+    A.seg_out_count = children_possible ? lc + (d + 1) * rr::LC_COUNT + rr::LC_SEG0 : nullptr;
+    // level d reads ev_b when d is even (d >= 2), ev_a when odd; writes the other one
+    A.ev = d == 0 ? nullptr : (d % 2 ? c->ev_a : c->ev_b).as<rr::Event>();
+    A.hit = c->hit.as<rr::HitRec>();
+    A.n12 = c->n12.as<double>();
+    A.comb = children_possible ? c->comb[d].as<rr::CombRec>() : nullptr;
+    A.parent_comb = d > 0 ? c->comb[d - 1].as<rr::CombRec>() : nullptr;
+    A.comb_ext = ext && children_possible ? c->comb_ext[d].as<rr::CombExt>() : nullptr;
+    A.parent_ext = ext && d > 0 ? c->comb_ext[d - 1].as<rr::CombExt>() : nullptr;
+    for (int q = 0; q <= RR_MAX_DEPTH; ++q) A.chain[q] = q + 1 < p.levels ? c->comb[q].as<rr::ChainRec>() : nullptr;
+    A.out = o.out;
+    A.avg = o.avg;
+    A.avg_f32 = o.avg_f32;
+    A.aa_wave = (d == 0 && A.tile_fast) ? o.aa_wave : 0;
+    A.pad_children = plan.pad_children ? 1 : 0;
+    // null when no material is reflective or transparent (or at the last level)
+    A.next = children_possible ? (d % 2 ? c->ev_b : c->ev_a).as<rr::Event>() : nullptr;
+    A.pending = children_possible ? c->pend[d].as<int32_t>() : nullptr;
+    A.n1n2_list = c->n1n2.as<int32_t>();
+    A.lcount = lc + d * rr::LC_COUNT;
+    if (plan.order.ok && d == 0) order_level0_args(c, plan, A);
+    A.counters = frame_counters(c, c->epoch);
+    A.counters_zero = (c->zero_next && d == 0 && base == 0) ? frame_counters(c, c->epoch ^ 1) : nullptr;
+    return A;
+}
+
+// The chain family's camera launch; with the deep queue (plan.spill) it appends the chains still reflecting at
+// RR_DEEP_FROM to the queue's segments, and a second launch (one block per segment) finishes them.
+hipError_t launch_chain_frame(rr_ctx* c, const rr::FramePlan& plan, rr::LevelArgs& A, hipStream_t st) {
+    if (!plan.spill) return rr::launch_chain(c->S, A, st, kprof(c));
+    A.deep = c->deep.as<rr::DeepRec>();
+    A.deep_from = rr::RR_DEEP_FROM;
+    A.nseg_out = (int32_t)plan.deep_nseg;
+    A.seg_out_count = c->deep_count.as<unsigned int>();
+    A.seg_cap_out = plan.deep_seg_cap;
+    hipError_t e = rr::launch_chain(c->S, A, st, kprof(c));
+    if (e != hipSuccess) return e;
+    rr::LevelArgs D = A;
+    D.nseg = (int32_t)plan.deep_nseg;
+    D.seg_count = A.seg_out_count;
+    D.seg_cap = plan.deep_seg_cap;
+    D.seg_out_count = nullptr;
+    D.counters_zero = nullptr;
+    return rr::launch_chain(c->S, D, st, kprof(c), true);
+}
+
+// A level-0-only frame that qualifies (plan.persist_candidate) runs as one resident launch when rr::persist_plan
+// agrees.  Its tile queue's heads are the C_WORK words of this frame's counter slots, which no kernel counts into:
+// zero like the rest of the buffer — at rr_create, or by the first kernels of the frame before (counters_zero).  A
+// frame that launches nothing (a part with no rows) zeroes nothing, and does not take the buffer either:
+// end_frame_counters leaves the untouched buffer to the next frame
+hipError_t launch_level0_frame(rr_ctx* c, const rr::FramePlan& plan, rr::LevelArgs& A, hipStream_t st) {
+    if (!plan.persist_candidate) return rr::launch_level(c->S, A, st, kprof(c));
+    A.persist_tiles = (uint32_t)(A.n / 64);
+    A.persist_heads = persist_heads();
+    A.persist_head = A.counters + rr::C_WORK;
+    const rr::PersistPlan persist = rr::persist_plan(c->S, A, &c->persist_resident);
+    if (persist.blocks <= 0) return rr::launch_level(c->S, A, st, kprof(c));
+    c->persist_last = persist;
+    return rr::launch_persist(c->S, A, persist, st, kprof(c));
+}
+
+hipError_t launch_family(rr_ctx* c, const rr::FramePlan& plan, rr::LevelArgs& A, hipStream_t st) {
+    const bool listed = A.list != nullptr;  // the plan admits the in-wave families only
+    switch (plan.family) {
+        case rr::Family::Tree:
+            return listed ? rr::launch_tree_listed(c->S, A, st, kprof(c)) : rr::launch_tree(c->S, A, st, kprof(c));
+        case rr::Family::Chain:
+            return listed ? rr::launch_chain_listed(c->S, A, st, kprof(c)) : launch_chain_frame(c, plan, A, st);
+        case rr::Family::Level0:
+            return listed ? rr::launch_level_listed(c->S, A, st, kprof(c)) : launch_level0_frame(c, plan, A, st);
+        case rr::Family::FusedLevels:
+        case rr::Family::Unfused:
+            break;
+    }
+    return rr::launch_level(c->S, A, st, kprof(c));
+}
+
+// bottom-up shade_hit sums of the events with children (scene.rs:172-177), for the unfused levels; fused levels
+// finish their chains in the kernels
+int combine_levels(rr_ctx* c, const rr::LevelArgs& base_args, const rr::FramePlan& plan, const rr::LevelPlan& p,
+                   int64_t base, const FrameOut& o, hipStream_t st) {
+    unsigned int* lc = c->lcount.as<unsigned int>();
+    for (int d = p.levels - 2; d >= 0; --d) {
+        rr::CombArgs C{};
+        C.level = d;
+        C.n = p.cap[d];
+        C.n_dev = lc + d * rr::LC_COUNT + rr::LC_PENDING;
+        C.base = base;
+        C.pending = c->pend[d].as<int32_t>();
+        C.comb = c->comb[d].as<rr::CombRec>();
+        C.parent_comb = d > 0 ? c->comb[d - 1].as<rr::CombRec>() : nullptr;
+        C.comb_ext = plan.ext ? c->comb_ext[d].as<rr::CombExt>() : nullptr;
+        C.parent_ext = plan.ext && d > 0 ? c->comb_ext[d - 1].as<rr::CombExt>() : nullptr;
+        C.out = o.out;
+        C.avg = o.avg;
+        C.avg_f32 = o.avg_f32;
+        C.hs = base_args.hs;
+        C.lrows = base_args.rays0 ? 0 : base_args.lrows;
+        HIPCHK(rr::launch_combine(C, st, kprof(c)));
+    }
+    return RR_OK;
+}
+
+// an AA pass: the output rows of the batch [base, base + nb), averaged on the second stream after the batch
+int average_pass(rr_ctx* c, const rr::FramePlan& plan, const FrameOut& o, int64_t hs, int64_t base, int64_t nb,
+                 hipStream_t st) {
+    const AaPasses& a = *o.aap;
+    const int64_t y0 = base / hs / a.aa, y1 = (base + nb) / hs / a.aa;
+    const size_t pi = (size_t)(base / plan.B);
+    while (c->pass_ev.size() <= pi) {
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->pass_ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(c->pass_ev[pi], st));
+    HIPCHK(hipStreamWaitEvent(c->aa_stream, c->pass_ev[pi], 0));
+    HIPCHK(launch_average(a, o.out + 3 * y0 * a.aa * hs, y0, y1 - y0, c->aa_stream, kprof(c)));
+    return RR_OK;
+}
+
+// Runs the wavefront levels for `total` level-0 events; level-0 rays come from the camera or from ctx->rays0
+// (color_at).  Results (color_at values) land in `out` (3 doubles per event), or averaged in `avg`.  facts: the
+// call's frame_facts for this max_depth.  frame_plan.hpp decides what runs; the steps below launch it.
+int run_levels(rr_ctx* c, const FrameFacts& facts, const rr::LevelArgs& base_args, int64_t total, int max_depth,
+               double* out, hipStream_t st, void* avg = nullptr, int32_t avg_f32 = 0, int32_t aa_wave = 0,
+               const AaPasses* aap = nullptr) {
+    const FrameOut o{out, avg, avg_f32, aa_wave, aap};
+    const rr::FramePlan plan = plan_run(c, facts, base_args, total, max_depth, o);
+    if (plan.err != RR_OK) return fail(plan.err, plan.msg);
+    int rc = grow_workspace(c, plan);
+    if (rc == RR_OK && plan.order.ok) rc = refresh_order(c, base_args, plan, !facts.sw.no_tile_guess, st);
+    if (rc != RR_OK) return rc;
+    for (int64_t base = 0; base < total; base += plan.B) {
+        const int64_t nb = std::min(plan.B, total - base);
+        rr::LevelPlan short_batch;
+        if (nb != plan.B) short_batch = rr::plan_levels(nb, plan.k, plan.plan_depth, plan.ext, plan.fused);
+        const rr::LevelPlan& p = nb != plan.B ? short_batch : plan.P;
+        // the queue counters are zeroed once per batch (appends, pending, n1/n2 lists): no memset in the frames of
+        // the in-wave chains and trees, which use none (it cost a C1 frame 9.6 us as two fills)
+        if (plan.zero_lcount)
+            HIPCHK(hipMemsetAsync(c->lcount.p, 0, (size_t)p.levels * rr::LC_COUNT * sizeof(unsigned int), st));
+        if (plan.spill) HIPCHK(hipMemsetAsync(c->deep_count.p, 0, (size_t)plan.deep_nseg * sizeof(unsigned int), st));
         for (int d = 0; d < p.levels; ++d) {
-            const bool children_possible = d + 1 < p.levels;
-            rr::LevelArgs A = base_args;
-            A.base = base;
-            set_level0_index(A);
-            A.level = d;
-            A.rem = max_depth - d;
-            A.n = p.cap[d];
-            A.n_dev = d > 0 ? lc + (d - 1) * rr::LC_COUNT + rr::LC_CHILDREN : listed ? base_args.n_dev : nullptr;
-            A.nseg = fused && d > 0 ? rr::RR_NSEG : 1;
-            A.nseg_out = fused ? rr::RR_NSEG : 1;
-            A.seg_cap = fused && d > 0 ? p.seg_cap[d] : 0;
-            A.seg_cap_out = fused && children_possible ? p.seg_cap[d + 1] : 0;
-            A.seg_count = lc + d * rr::LC_COUNT + rr::LC_SEG0;
-            A.seg_out_count = children_possible ? lc + (d + 1) * rr::LC_COUNT + rr::LC_SEG0 : nullptr;
-            // level d reads ev_b when d is even (d >= 2), ev_a when odd; writes the other one
-            A.ev = d == 0 ? nullptr : (d % 2 ? c->ev_a : c->ev_b).as<rr::Event>();
-            A.hit = c->hit.as<rr::HitRec>();
-            A.n12 = c->n12.as<double>();
-            A.comb = children_possible ? c->comb[d].as<rr::CombRec>() : nullptr;
-            A.parent_comb = d > 0 ? c->comb[d - 1].as<rr::CombRec>() : nullptr;
-            A.comb_ext = ext && children_possible ? c->comb_ext[d].as<rr::CombExt>() : nullptr;
-            A.parent_ext = ext && d > 0 ? c->comb_ext[d - 1].as<rr::CombExt>() : nullptr;
-            for (int q = 0; q <= RR_MAX_DEPTH; ++q)
-                A.chain[q] = q + 1 < p.levels ? c->comb[q].as<rr::ChainRec>() : nullptr;
-            A.out = out;
-            A.avg = avg;
-            A.avg_f32 = avg_f32;
-            A.aa_wave = (d == 0 && A.tile_fast) ? aa_wave : 0;
-            if (A.pw) {  // pixel waves: the launch holds whole waves of 7 pixels (one batch, chain kernels only)
-                if (!chain || B < total) return fail(RR_E_ARG, "internal: pixel waves need one chain-kernel batch");
-                A.n = pixel_waves(A) * 64;
-            }
-            // fused levels queue each wave's reflected rays in a 64-slot block of its own, at the lanes they
-            // left (holes marked): a secondary wave is one camera tile's rays, as coherent as they come.
-            // Packed queues mixed 2-4 tiles per wave (C3 10.54 -> 8.98 ms with the blocks); the area-light
-            // scenes' block-wide sample dealing prefers packed waves (C5 2.27 vs 2.30 ms)
-            A.pad_children = fused && !c->S.has_area ? 1 : 0;
+            rr::LevelArgs A = level_args(c, base_args, plan, p, base, d, max_depth, o);
             if (aa_wave && !A.aa_wave) return fail(RR_E_ARG, "internal: in-wave AA average without full tiles");
-            // null when no material is reflective or transparent (or at the last level)
-            A.next = children_possible ? (d % 2 ? c->ev_b : c->ev_a).as<rr::Event>() : nullptr;
-            A.pending = children_possible ? c->pend[d].as<int32_t>() : nullptr;
-            A.n1n2_list = c->n1n2.as<int32_t>();
-            A.lcount = lc + d * rr::LC_COUNT;
-            if (order_ok && d == 0) {
-                A.tile_perm = c->order_valid ? c->tile_perm.as<uint32_t>() : nullptr;
-                // the waves record their costs only in a frame the sort below reads (every kRR_ORDER_EVERY-th):
-                // each record is one scattered 4-byte store per wave, a partial line that L2 writes back alone
-                // (47 MB of the C3 chain kernel's 0.55 GB of writes per frame, profiles/r05/attrib_c3.txt)
-                const bool sort_after = !c->order_valid || c->order_age + 1 >= kRR_ORDER_EVERY;
-                A.tile_cost = sort_after ? c->tile_cost.as<uint32_t>() : nullptr;
-                A.order_group = order_group;
-            }
-            A.counters = frame_counters(c, c->epoch);
-            A.counters_zero = (c->zero_next && d == 0 && base == 0) ? frame_counters(c, c->epoch ^ 1) : nullptr;
-            // a one-level, one-batch frame of full tiles may run as one resident launch (rr::persist_plan decides,
-            // below).  Its tile queue's heads are the C_WORK words of this frame's counter slots, which no kernel
-            // counts into: zero like the rest of the buffer — at rr_create, or by the first kernels of the frame
-            // before (counters_zero above).  A frame that launches nothing (a part with no rows) zeroes nothing, and
-            // does not take the buffer either: end_frame_counters leaves the untouched buffer to the next frame
-            rr::PersistPlan persist{0, 0};
-            if (fused && !chain && !tree && !listed && p.levels == 1 && B >= total && A.tile_fast && !A.pw &&
-                nb % 64 == 0 && nb / 64 < ((int64_t)1 << 31) && c->zero_next) {
-                A.persist_tiles = (uint32_t)(nb / 64);
-                A.persist_heads = persist_heads();
-                A.persist_head = A.counters + rr::C_WORK;
-                persist = rr::persist_plan(c->S, A, &c->persist_resident);
-            }
-            if (persist.blocks > 0) c->persist_last = persist;
-            if (listed) {
-                rr::KernelProf* kp = c->profile ? &c->prof : nullptr;
-                HIPCHK(tree ? rr::launch_tree_listed(c->S, A, st, kp)
-                            : chain ? rr::launch_chain_listed(c->S, A, st, kp) : rr::launch_level_listed(c->S, A, st, kp));
-            } else if (tree) {
-                HIPCHK(rr::launch_tree(c->S, A, st, c->profile ? &c->prof : nullptr));
-            } else if (chain) {
-                if (spill) {  // camera launch appends to the deep queue's segments (level 1's counters)
-                    A.deep = c->deep.as<rr::DeepRec>();
-                    A.deep_from = rr::RR_DEEP_FROM;
-                    A.nseg_out = (int32_t)deep_nseg;
-                    A.seg_out_count = c->deep_count.as<unsigned int>();
-                    A.seg_cap_out = deep_seg_cap;
-                }
-                HIPCHK(rr::launch_chain(c->S, A, st, c->profile ? &c->prof : nullptr));
-                if (spill) {  // the deep launch: one block per segment
-                    rr::LevelArgs D = A;
-                    D.nseg = (int32_t)deep_nseg;
-                    D.seg_count = A.seg_out_count;
-                    D.seg_cap = deep_seg_cap;
-                    D.seg_out_count = nullptr;
-                    D.counters_zero = nullptr;
-                    HIPCHK(rr::launch_chain(c->S, D, st, c->profile ? &c->prof : nullptr, true));
-                }
-            } else if (persist.blocks > 0) {
-                HIPCHK(rr::launch_persist(c->S, A, persist, st, c->profile ? &c->prof : nullptr));
-            } else {
-                HIPCHK(rr::launch_level(c->S, A, st, c->profile ? &c->prof : nullptr));
-            }
+            HIPCHK(launch_family(c, plan, A, st));
             if (A.counters_zero) c->next_zeroed = true;  // the launch above clears the next frame's buffer
-            if (order_ok && d == 0 && (!c->order_valid || ++c->order_age >= kRR_ORDER_EVERY)) {
-                HIPCHK(rr::launch_tile_order(c->tile_cost.as<uint32_t>(), c->tile_perm.as<uint32_t>(),
-                                             c->tile_hist.as<uint32_t>(), n_tiles, order_group, st));
-                c->order_valid = true;
-                c->order_age = 0;
-            }
+            if (plan.order.ok && d == 0 && (rc = age_order(c, plan, st)) != RR_OK) return rc;
         }
-        // bottom-up shade_hit sums of the events with children (scene.rs:172-177); fused levels finish
-        // their chains in the kernels
-        for (int d = p.levels - 2; d >= 0 && !rr::fused_levels(c->S); --d) {
-            rr::CombArgs C{};
-            C.level = d;
-            C.n = p.cap[d];
-            C.n_dev = lc + d * rr::LC_COUNT + rr::LC_PENDING;
-            C.base = base;
-            C.pending = c->pend[d].as<int32_t>();
-            C.comb = c->comb[d].as<rr::CombRec>();
-            C.parent_comb = d > 0 ? c->comb[d - 1].as<rr::CombRec>() : nullptr;
-            C.comb_ext = ext ? c->comb_ext[d].as<rr::CombExt>() : nullptr;
-            C.parent_ext = ext && d > 0 ? c->comb_ext[d - 1].as<rr::CombExt>() : nullptr;
-            C.out = out;
-            C.avg = avg;
-            C.avg_f32 = avg_f32;
-            C.hs = base_args.hs;
-            C.lrows = base_args.rays0 ? 0 : base_args.lrows;
-            HIPCHK(rr::launch_combine(C, st, c->profile ? &c->prof : nullptr));
-        }
-        if (passes) {  // this batch's output rows, averaged on the second stream after the batch
-            const int64_t y0 = base / base_args.hs / aap->aa, y1 = (base + nb) / base_args.hs / aap->aa;
-            const size_t pi = (size_t)(base / B);
-            while (c->pass_ev.size() <= pi) {
-                hipEvent_t e = nullptr;
-                HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                c->pass_ev.push_back(e);
-            }
-            HIPCHK(hipEventRecord(c->pass_ev[pi], st));
-            HIPCHK(hipStreamWaitEvent(c->aa_stream, c->pass_ev[pi], 0));
-            const double* src = out + 3 * y0 * aap->aa * base_args.hs;
-            if (aap->f32)
-                HIPCHK(rr::launch_aa_f32(src, static_cast<float*>(aap->avg) + 3 * y0 * aap->width, aap->width, y1 - y0,
-                                         aap->aa, c->aa_stream, c->profile ? &c->prof : nullptr));
-            else
-                HIPCHK(rr::launch_aa(src, static_cast<double*>(aap->avg) + 3 * y0 * aap->width, aap->width, y1 - y0,
-                                     aap->aa, c->aa_stream, c->profile ? &c->prof : nullptr));
-        }
+        if (plan.family == rr::Family::Unfused) rc = combine_levels(c, base_args, plan, p, base, o, st);
+        if (rc == RR_OK && plan.passes) rc = average_pass(c, plan, o, base_args.hs, base, nb, st);
+        if (rc != RR_OK) return rc;
     }
-    if (passes) {  // the caller's stream continues after the last pass's average
+    if (plan.passes) {  // the caller's stream continues after the last pass's average
         HIPCHK(hipEventRecord(c->aa_done, c->aa_stream));
         HIPCHK(hipStreamWaitEvent(st, c->aa_done, 0));
     } else if (aap) {  // one pass: the average follows on the caller's stream
-        const int64_t rows = total / base_args.hs / aap->aa;
-        if (aap->f32)
-            HIPCHK(rr::launch_aa_f32(out, static_cast<float*>(aap->avg), aap->width, rows, aap->aa, st,
-                                     c->profile ? &c->prof : nullptr));
-        else
-            HIPCHK(rr::launch_aa(out, static_cast<double*>(aap->avg), aap->width, rows, aap->aa, st,
-                                 c->profile ? &c->prof : nullptr));
+        HIPCHK(launch_average(*aap, out, 0, total / base_args.hs / aap->aa, st, kprof(c)));
     }
     return RR_OK;
 }
@@ -1099,46 +1126,32 @@ int rr_render_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, v
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     HIPCHK(claim_stream(c, st));
     StreamClaim claim{c, st};
-    // aa == 1, or aa in {2, 4, 8} without secondary rays (wave_avg_ok): the average is written by the
+    // aa == 1, the level-0 waves' own average or pixel waves (rr::plan_output): the average is written by the
     // kernels directly; the canvas only when asked for
-    const bool wave_avg = d_avg && wave_avg_ok(c, o->aa, cam->hsize, local_rows, o->max_depth);
-    // aa == 3 frames with reflection chains: pixel waves (7 whole pixels per wave) average in the wave too
-    const bool pw = d_avg && !wave_avg && o->aa == 3 &&
-                    (rr::tree_levels(c->S) || rr::chain_levels(c->S, c->host.max_children, o->max_depth)) &&
-                    block % 2 == 0 && total <= c->batch && !std::getenv("RRAY_NO_PW");
-    const bool direct_avg = d_avg && (o->aa == 1 || wave_avg || pw);
+    const FrameFacts facts = frame_facts(c, o->max_depth);
+    const rr::OutputPlan mode = rr::plan_output(facts.traits, facts.sw, d_avg != nullptr, o->aa, cam->hsize, local_rows,
+                                                o->max_depth, block, c->batch);
     double* canvas = static_cast<double*>(d_canvas);
-    if (!canvas && !direct_avg) {
+    if (!canvas && !mode.direct_avg) {
         HIPCHK(c->canvas.ensure(std::max<int64_t>(total, 1) * 3 * sizeof(double)));
         canvas = c->canvas.as<double>();
     }
     c->frame_timed = !(o->flags & RR_NO_FRAME_TIMING);
     if (c->frame_timed) HIPCHK(hipEventRecord(c->e0, st));
-    rr::LevelArgs A{};
-    A.cam = dev_camera(cam);
-    A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
-                   A.cam.origin[3] == 1.0;
-    A.hs = cam->hsize;
+    rr::LevelArgs A = camera_args(cam, o, o->aa, part, block);
     A.lrows = local_rows;
-    A.aa = o->aa;
-    A.part = part;
-    A.nparts = o->nparts;
-    A.block_rows = block;
-    A.rays0 = nullptr;
-    A.seed = o->seed;
-    A.jitter_mode = o->jitter_mode;
-    if (pw) {
+    if (mode.pw) {
         A.pw = 1;
         A.pw_rows = (int32_t)rows;
-        A.pw_wpb = (uint32_t)((2 * W + 6) / 7);
+        A.pw_wpb = mode.pw_wpb;
     }
     const int32_t f32 = (o->flags & RR_OUT_AVG_F32) ? 1 : 0;
     rc = tile_bundles(c, A, st, &A.tile_bundles);
     if (rc != RR_OK) return rc;
     begin_frame_counters(c);
     const AaPasses aap{d_avg, f32, W, o->aa};
-    rc = run_levels(c, A, total, o->max_depth, canvas, st, direct_avg ? d_avg : nullptr, f32, wave_avg ? o->aa : 0,
-                    (d_avg && !direct_avg) ? &aap : nullptr);
+    rc = run_levels(c, facts, A, total, o->max_depth, canvas, st, mode.direct_avg ? d_avg : nullptr, f32,
+                    mode.wave_avg ? o->aa : 0, (d_avg && !mode.direct_avg) ? &aap : nullptr);
     c->zero_next = false;
     if (rc != RR_OK) return rc;
     end_frame_counters(c);
@@ -1278,7 +1291,7 @@ int rr_color_at(rr_ctx* c, int64_t n, const double* origins, const double* direc
     A.rays0 = c->rays0.as<double>();
     A.seed = seed;
     A.jitter_mode = jitter_mode;
-    int rc = run_levels(c, A, n, remaining, c->qout.as<double>(), st);
+    int rc = run_levels(c, frame_facts(c, remaining), A, n, remaining, c->qout.as<double>(), st);
     c->epoch = saved_epoch;
     if (rc != RR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out_rgb, c->qout.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1424,9 +1437,7 @@ int rr_render_aov_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* 
     HIPCHK(hipEventRecord(c->e0, st));
     HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
     rr::LevelArgs A{};
-    A.cam = dev_camera(cam);
-    A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
-                   A.cam.origin[3] == 1.0;
+    set_camera(A, cam);
     A.hs = cam->hsize;
     A.lrows = cam->vsize;
     A.aa = o->aa;
@@ -1521,10 +1532,8 @@ int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_o
         return fail(RR_E_LIMIT, "an adaptive frame must hold fewer than 2^32 samples");
     const int64_t total = W * H * aa * aa;  // the refine pass's capacity: every pixel listed
     if (total > c->batch) return fail(RR_E_LIMIT, "an adaptive frame's samples must fit one pass of the context");
-    const bool tree = rr::tree_levels(c->S);
-    const bool in_wave = tree || rr::chain_levels(c->S, c->host.max_children, o->max_depth) ||
-                         (rr::fused_levels(c->S) && (c->host.max_children == 0 || o->max_depth == 0));
-    if (!in_wave)
+    const FrameFacts facts = frame_facts(c, o->max_depth);
+    if (!rr::in_wave(rr::frame_family(facts.traits, o->max_depth)))
         return fail(RR_E_ARG, "adaptive frames are not served by the per-level paths (RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN)");
     // 1. the probe's camera and options: the aa 1 frame of the same view
     rr_camera cam1;
@@ -1543,29 +1552,14 @@ int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_o
     c->frame_timed = !(o->flags & RR_NO_FRAME_TIMING);
     if (c->frame_timed) HIPCHK(hipEventRecord(c->e0, st));
     const int32_t block = o->block_rows > 0 ? o->block_rows : 8;
-    const auto camera_args = [&](const rr_camera* cm, int32_t a) {
-        rr::LevelArgs A{};
-        A.cam = dev_camera(cm);
-        A.cam_affine = A.cam.inv[12] == 0.0 && A.cam.inv[13] == 0.0 && A.cam.inv[14] == 0.0 && A.cam.inv[15] == 1.0 &&
-                       A.cam.origin[3] == 1.0;
-        A.hs = cm->hsize;
-        A.aa = a;
-        A.part = 0;
-        A.nparts = 1;
-        A.block_rows = block;
-        A.rays0 = nullptr;
-        A.seed = o->seed;
-        A.jitter_mode = o->jitter_mode;
-        return A;
-    };
     // the probe is rr_render_device's aa 1 frame, launch for launch: straight into d_avg; its first kernels zero the
     // next frame's counters
-    rr::LevelArgs A1 = camera_args(&cam1, 1);
+    rr::LevelArgs A1 = camera_args(&cam1, o, 1, 0, block);  // part 0 of 1 (adaptive_check_args)
     A1.lrows = H;
     rc = tile_bundles(c, A1, st, &A1.tile_bundles);
     if (rc != RR_OK) return rc;
     begin_frame_counters(c);
-    rc = run_levels(c, A1, W * H, o->max_depth, nullptr, st, d_avg, 0, 0, nullptr);
+    rc = run_levels(c, facts, A1, W * H, o->max_depth, nullptr, st, d_avg, 0, 0, nullptr);
     c->zero_next = false;
     if (rc != RR_OK) return rc;
     // 2. mask, ordered compaction: the list and its length stay on the device
@@ -1587,12 +1581,12 @@ int rr_render_adaptive_device(rr_ctx* c, const rr_camera* cam, const rr_render_o
     if (aa > 1) {
         // 3. the refine pass: the listed pixels' samples through the scene's own kernel family, counted into the
         // probe's counters (same epoch, nothing zeroed); launched for the capacity, the live count is P.counts[1]
-        rr::LevelArgs A2 = camera_args(cam, aa);
+        rr::LevelArgs A2 = camera_args(cam, o, aa, 0, block);
         A2.lrows = 0;  // no tile layout: events are list entries
         A2.list = P.list;
         A2.list_w = (uint32_t)W;
         A2.n_dev = P.counts + 1;
-        rc = run_levels(c, A2, total, o->max_depth, c->canvas.as<double>(), st);
+        rc = run_levels(c, facts, A2, total, o->max_depth, c->canvas.as<double>(), st);
         if (rc != RR_OK) return rc;
         // 4. canvas.rs:85-96 per listed pixel, over its aa 1 colour
         HIPCHK(rr::launch_adapt_resolve(P, st));
