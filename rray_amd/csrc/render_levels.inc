@@ -75,8 +75,11 @@ __global__ void __launch_bounds__(256) n1n2_kernel(DevScene S, LevelArgs A) {
 }
 
 
-// floor(n / d) for a wave-uniform d >= 1 and n < 2^24, given rd = 1.0f / d: the f32 quotient is
-// within one of the true one, and two integer corrections make it exact
+// floor(n / d) for a wave-uniform d >= 1, given rd = 1.0f / d, wherever the quotient is below 2^22 and n + 2 d below
+// 2^32: (float)n, rd and their product each round once (relative 2^-24), so the f32 quotient is off by less than
+// 3 * 2^-24 * 2^22 < 1, its truncation within one of the true floor, and two integer corrections make it exact.  n itself
+// may pass 2^24: area_shadow_block's pairs reach 2^28 with quotients of at most 256 (the block's events) and its cell
+// indices 2^20 with quotients below 1024 (tests/test_division.py tries both call sites' whole domain)
 __device__ __forceinline__ uint32_t small_div(uint32_t n, uint32_t d, float rd) {
     uint32_t q = (uint32_t)((float)n * rd);
     if (q * d > n) --q;

@@ -20,6 +20,9 @@ configs never do:
   many      600-900 spheres of mixed scale (culls too large for LDS: the global-memory cull kernels)
   general   cubes and cylinders inside sheared groups (the G = 2 kernels)
 
+build_area, build_own, build_general and build_area_mix (area lights across every kernel variant, light mix and level)
+follow the same pattern with families of their own.
+
 Shininess is 200 everywhere so the specular power takes the correctly rounded path:
 any difference from the oracle is then a walk / cull error, never a last-ulp `pow`.
 """
@@ -494,7 +497,7 @@ def _pattern_tree(P, rng, level=0):
     return P.pat(kind, a=a, b=b, scale=float(rng.uniform(0.0, 1.0)), transform=tr)
 
 
-def build_general(seed):
+def build_general(seed, light=None, family=None, rng_base=40_000):
     """Scenes for the general kernels (the G = 2 variant: EntriesT<4>, csg_eval, quartic.inc, pattern_tree, texture_at),
     families by seed % 6:
 
@@ -506,9 +509,13 @@ def build_general(seed):
       textures  numpy textures of 1-6 x 1-6 texels on every shape kind
       mixed     everything inside sheared groups, reflective and glass materials, recursion depth 5
 
-    -> (Pair, camera spec, max_depth, family); Pair.featured holds the builder ids of the family's featured leaves."""
-    rng = np.random.default_rng(40_000 + seed)
-    cat = GENERAL[seed % len(GENERAL)]
+    -> (Pair, camera spec, max_depth, family); Pair.featured holds the builder ids of the family's featured leaves.
+
+    build_area_mix's `general` family passes light(P, rng, s), which adds the scene's lights in place of the one point
+    light (s: the scene's scale), the family by name and its own seed base; the seeded scenes of this builder itself
+    are untouched by those arguments."""
+    rng = np.random.default_rng(rng_base + seed)
+    cat = family or GENERAL[seed % len(GENERAL)]
     P = Pair()
     M = P.M
     P.featured = set()
@@ -599,10 +606,389 @@ def build_general(seed):
     floor = P.obj("plane", M.translate(0.0, -3.0 * s, 0.0), _material(rng, 0.4 if cat == "mixed" else 0.0), floor_col)
     if cat == "patterns":
         P.featured.add(floor)
-    P.light(rng.uniform(-20, 20, 3) * s + [0, 25 * s, -10 * s])
+    if light is None:
+        P.light(rng.uniform(-20, 20, 3) * s + [0, 25 * s, -10 * s])
+    else:
+        light(P, rng, s)
     up = (0.0, 1.0, 0.0)
     P.log.append(f"camera from={frm} to={to} up={up} fov={fov} depth={depth}")
     return P, {"from_": tuple(float(x) for x in frm), "to": to, "up": up, "fov": fov}, depth, cat
+
+
+AREA_MIX = ["nodes", "lights", "levels", "general", "patterns", "glass", "degenerate", "umbra"]
+AREA_MIX_SEEDS = range(64)
+MIX_NODE_COUNTS = (8, 9, 32, 33, 64, 65, 150, 600)  # `nodes`: the flattened node count per seed // 8
+MIX_LEVELS = (1, 5, 7, 16, 17, 33, 64, 181)         # `levels`: the area light's level per seed // 8
+MIX_LEVELS_SIZE = (16, 12)                           # `levels`: its frames (the oracle casts level^2 rays per event)
+MIX_BLACK_LIGHT, MIX_BLACK_SURFACE = 3, 4            # seed // 8 of a family's all-black light / all-black surface
+# What the dispatch reads, per family and k = seed // 8, set and not drawn: (G, light kinds in order, complex pattern,
+# transparent).  G: 0 flat, 1 groups, 2 general.  "A" an area light, "p" a point light; None: drawn by the family, the
+# number given.  Three or more lights switch the prelit stage off (kernels.hpp RR_PRELIT_LIGHTS).
+MIX_ATTRS = {
+    "nodes": [(0, "A", 0, 0), (0, "AA", 0, 0), (0, "A", 1, 0), (0, "AAp", 0, 0), (0, "A", 0, 0), (0, "AA", 1, 0),
+              (0, "A", 0, 0), (0, "AA", 0, 0)],
+    "lights": [(0, "AA", 0, 0), (1, "Ap", 1, 0), (2, "pA", 1, 0), (0, "ApA", 1, 0), (1, 4, 1, 0), (2, 5, 1, 0), (0, 3, 0, 0),
+               (1, 4, 0, 0)],
+    "levels": [(0, "A", 0, 0), (1, "A", 0, 0), (2, "A", 0, 0), (0, "Ap", 0, 0), (1, "A", 0, 0), (2, "pAp", 0, 0),
+               (0, "A", 0, 0), (1, "A", 0, 0)],
+    "general": [(2, "A" if not k & 1 else "pAA" if k & 2 else "ApA", (k >> 1) & 1, (k >> 2) & 1) for k in range(8)],
+    "patterns": [(2, "A", 1, 1), (0, "ApA", 1, 1), (1, "pAA", 1, 1), (2, "AAp", 1, 1), (1, "A", 1, 0), (2, "ApA", 1, 0),
+                 (0, "A", 1, 0), (1, "pAA", 1, 0)],
+    "glass": [(0, "A", 0, 1), (1, "A", 0, 1), (2, "A", 0, 1), (0, "ApA", 0, 1), (1, "pAA", 0, 1), (2, "AAp", 0, 1),
+              (0, "A", 1, 1), (1, "A", 1, 1)],
+    "degenerate": [(0, "A", 0, 0), (0, "A", 0, 0), (0, "A", 0, 0), (0, "AAp", 0, 0), (0, "A", 0, 0), (0, "AA", 0, 0),
+                   (0, "A", 0, 0), (0, "AA", 0, 0)],
+    "umbra": [(0, "A", 0, 0), (0, "A", 0, 0), (0, "A", 0, 0), (0, "AA", 0, 0), (0, "A", 0, 0), (0, "A", 0, 0),
+              (0, "Ap", 0, 0), (0, "A", 0, 0)],
+}
+
+
+def mix_attrs(seed):
+    """(G, light kinds or their number, complex pattern, transparent) of build_area_mix(seed), from MIX_ATTRS"""
+    return MIX_ATTRS[AREA_MIX[seed % 8]][(seed // 8) % 8]
+
+
+def _n_lights(kinds):
+    return kinds if isinstance(kinds, int) else len(kinds)
+
+
+# the depth-0 frames: the first scene without glass of every (G, PRE, CP); at depth 0 it takes the fused level-0 kernel
+MIX_DEPTH0_SEEDS = [next(s for s in AREA_MIX_SEEDS if not mix_attrs(s)[3] and
+                         (mix_attrs(s)[0], _n_lights(mix_attrs(s)[1]) <= 2, mix_attrs(s)[2]) == (g, pre, cp))
+                    for g in (0, 1, 2) for pre in (True, False) for cp in (0, 1)]
+
+
+def _light_color(rng):
+    """a random light colour, brighter or dimmer than white per channel, one channel exactly zero at times"""
+    c = [float(round(x, 3)) for x in rng.uniform(0.2, 1.3, 3)]
+    if rng.random() < 0.4:
+        c[int(rng.integers(3))] = 0.0
+    return tuple(c)
+
+
+class _Area:
+    """one area light's numbers before it is added: corner, u, v, level; its centre qc and half diagonal qr"""
+
+    def __init__(self, corner, u, v, level):
+        self.corner, self.u, self.v, self.level = (np.array(corner, float), np.array(u, float), np.array(v, float),
+                                                   int(level))
+        self.qc = self.corner + 0.5 * self.u + 0.5 * self.v
+        self.qr = 0.5 * max(np.linalg.norm(self.u + self.v), np.linalg.norm(self.u - self.v))
+
+
+def _area_above(rng, level, sizes=(1.5, 3.0, 6.0), S=1.0):
+    """a parallelogram above the scene like build_area's, but wide: penumbrae of a few samples' width"""
+    size = float(rng.choice(sizes)) * S
+    corner = np.array([rng.uniform(-5, 5), rng.uniform(4, 8), rng.uniform(-2, 9)]) * S
+    u = (np.array([1.0, 0.0, 0.0]) if rng.random() < 0.6 else _unit(rng)) * size
+    v = (np.array([0.0, 0.0, 1.0]) if rng.random() < 0.5 else _unit(rng)) * size * rng.uniform(0.4, 1.2)
+    return _Area(corner - 0.5 * u - 0.5 * v, u, v, level)
+
+
+def _mix_levels(rng, n):
+    """n different levels, small ones (the frames stay quick), at least one odd and one a power of two"""
+    return [int(x) for x in rng.permutation([2, 3, 4, 5, 6, 8])[:n]]
+
+
+def _draw_kinds(rng, n):
+    """n >= 3 light kinds in a drawn order, at least two of them area lights"""
+    kinds = ["A", "A"] + [str(rng.choice(["A", "p"])) for _ in range(n - 2)]
+    return "".join(kinds[i] for i in rng.permutation(n))
+
+
+def _back_point(rng, S=1.0):
+    """a point light low behind the scene: the sides of the objects that face the camera lie behind it"""
+    return np.array([rng.uniform(-6, 6), rng.uniform(0.3, 2.5), rng.uniform(5, 10)]) * S
+
+
+def _add_lights(P, rng, kinds, areas, k, S=1.0, points=None):
+    """The lights in the order of `kinds`.  The family's all-black light, in its MIX_BLACK_LIGHT scene, is the scene's last
+    point light, or its last light where it has none (MIX_ATTRS gives `nodes` and `degenerate` a point light there): a
+    black light's lanes are counted and never walked, so it must not be a light whose geometry the scene is about."""
+    areas, points = list(areas), list(points or [])
+    black = max(kinds.rfind("p"), -1) if "p" in kinds else len(kinds) - 1
+    for i, c in enumerate(kinds):
+        col = (0.0, 0.0, 0.0) if k == MIX_BLACK_LIGHT and i == black else _light_color(rng)
+        if c == "A":
+            a = areas.pop(0)
+            P.area_light(a.corner, a.u, a.v, a.level, col)
+        else:
+            P.light(points.pop(0) if points else _back_point(rng, S), col)
+        P.log[-1] += f" colour={col}"
+
+
+def _capsule_point(rng, area, r, S=1.0):
+    """build_area's rule: a centre at distance ~ r + qr t from the segment between a visible floor point and the light's
+    centre, just inside or just outside the light hull of that point"""
+    fp = np.array([rng.uniform(-3, 3), 0.0, rng.uniform(-1, 5)]) * S
+    t = rng.uniform(0.1, 0.6)
+    a = fp + t * (area.qc - fp)
+    off = (r + area.qr * t) * (1.0 + float(rng.choice([-1e-3, 1e-6, 1e-3, 0.05, -0.05, -0.5, -0.9])))
+    return a + _unit(rng) * off
+
+
+def _mix_content(P, rng, areas, G, n, k, cp=False, glass=False, patterned=False, S=1.0, reflective_p=0.4):
+    """A floor and n occluders under the lights `areas`: spheres (G = 2: every other a cube) by the capsule rule, turn
+    by turn per light; G >= 1: every other one inside a scaled and sheared group, with a plane far behind the scene in a
+    group of its own.  cp: the floor carries a gradient (a complex pattern whatever the trees draw); patterned: pattern
+    trees and textures on the floor and the occluders; glass: one occluder in three is glass and one is for certain.
+    The floor is reflective, so a scene without glass takes the chain kernel at its depth.  The family's all-black surface
+    (no diffuse, no specular term under any light) is the first occluder of its MIX_BLACK_SURFACE scene."""
+    M = P.M
+
+    def colour():
+        if patterned and rng.random() < 0.7:
+            if rng.random() < 0.3:
+                img = rng.integers(0, 256, (int(rng.integers(1, 5)), int(rng.integers(1, 5)), 4), dtype=np.uint8)
+                return P.pat("texture", a=P.tex(img))
+            return _pattern_tree(P, rng)
+        return _color(rng)
+
+    floor_col = colour()
+    if cp:
+        floor_col = P.pat("gradient", a=P.pat("solid", _color(rng)), b=floor_col if isinstance(floor_col, Pat) else
+                          P.pat("solid", floor_col), transform=M.scale(3.0 * S, 3.0 * S, 3.0 * S))
+    fm = _material(rng, 0.0)
+    P.obj("plane", M.identity(), fm[:4] + (float(rng.choice([0.2, 0.4])), 0.0, 1.0), floor_col)
+    group, ginv = -1, None
+    if G >= 1:
+        gt = _mul(M, M.scale(*rng.uniform(0.6, 1.6, 3)), M.shear(*[float(x) for x in rng.uniform(-0.4, 0.4, 6)]),
+                  M.translate(*[float(x) for x in rng.uniform(-1, 1, 3) * S]))
+        group, ginv = P.obj("group", gt), M.inverse(gt)
+        back = P.obj("group", M.translate(0.0, 0.0, 14.0 * S))
+        P.obj("plane", M.rotate("x", math.pi / 2), _material(rng), _color(rng), parent=back)
+    for i in range(n):
+        r = _logu(rng, 0.15, 0.9) * S
+        c = _capsule_point(rng, areas[i % len(areas)], r, S)
+        c[1] = max(c[1], 0.3 * r)
+        if i == 0:  # a large one on the visible floor: a core of full shadow, a side turned away from the lights
+            r = float(rng.uniform(0.9, 1.5)) * S
+            c = np.array([rng.uniform(-2, 2) * S, 0.7 * r, rng.uniform(1, 4) * S])
+        m7 = _material(rng, reflective_p)
+        col = colour()
+        if glass and (i == 1 or rng.random() < 0.33):
+            m7 = m7[:4] + (float(rng.choice([0.0, 0.3, 0.9])), float(rng.choice([0.5, 0.9, 1.0])),
+                           float(rng.choice([1.33, 1.5, 2.4])))
+        if i == 0 and k == MIX_BLACK_SURFACE:
+            m7, col = (m7[0], m7[1], 0.0, SHININESS, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0)
+        tr = _mul(M, M.scale(r, r, r), M.translate(*[float(x) for x in c]))
+        kind = "sphere"
+        if G == 2 and i % 2 == 0:
+            kind, tr = "cube", _mul(M, M.scale(r, r * rng.uniform(0.3, 1.5), r), _rot(M, rng), M.translate(*[float(x) for x in c]))
+        parent = group if G >= 1 and i % 2 == 1 else -1
+        P.obj(kind, M.multiply(ginv, tr) if parent >= 0 else tr, m7, col, parent)
+
+
+def _mix_camera(rng, S=1.0):
+    frm = (float(rng.uniform(-2, 2)) * S, float(rng.uniform(1.5, 4)) * S, -6.0 * S)
+    return {"from_": frm, "to": (0.0, 0.5 * S, 2.0 * S), "up": (0.0, 1.0, 0.0), "fov": float(rng.uniform(0.8, 1.2))}
+
+
+def build_area_mix(seed):
+    """Area lights across every kernel variant, light mix and level (tests/test_gpu_fuzz.py
+    test_area_mix_fuzz_bit_exact): what build_area leaves out.  Eight families by seed % 8; inside a family k = seed // 8
+    sets what the dispatch reads from MIX_ATTRS (G, the lights' kinds and order, a complex pattern, transparency), so
+    the coverage table of tests/test_area_mix_host.py holds by construction.  Lights take random colours, some with a
+    zero channel; every family holds an all-black light (k = 3) and an all-black surface (k = 4).
+
+      nodes       flat scenes of exactly 8, 9, 32, 33, 64, 65, 150 and 600 nodes (a floor, a wall in the odd ones, spheres)
+                  under one or two area lights: the per-node regime (RR_BUNDLE_MIN_NODES), the 32-bit node mask, the hull
+                  pre-test's limit (RR_AREA_PRETEST_NODES) and, at 600 nodes, culls in global memory.  Capsule-rule
+                  occluders are the first and the last spheres added, small clutter between them.  The flattening
+                  orders the nodes itself (flatten.cpp: leaves in Morton order, the planes last), so where an occluder
+                  lands follows from its position: from 64 nodes on some land at node indices >= 32
+                  (tests/test_area_mix_host.py asserts it from node_of_object); in the 33-node scene nodes 31 and 32
+                  are the floor and the wall.  The 33-node scene has a third, black point light
+      lights      2 to 5 lights: area + area, area + point, point + area, then three and more in a drawn order with at
+                  least two area lights of different level (the stage's reuse, li in the jitter key, the LDS layout
+                  behind n_lights prelit terms); flat, grouped and general in turn
+      levels      level 1, 5, 7, 16, 17, 33, 64 and 181 (frames of MIX_LEVELS_SIZE)
+      general     an area light over build_general's content: cones, tori, nested CSG, patterns, everything mixed in
+                  sheared groups, planes inside groups (unbounded culls: the pre-test's `pass = true` branch)
+      patterns    pattern trees and small textures on the floor and the occluders, under one and three lights
+      glass       transparent and reflective materials under one and three lights, flat, grouped and general; depth 4
+      degenerate  valid scenes at the edges of the pre-tests' geometry, by k: v the zero vector; u parallel to v; a light
+                  that crosses the floor; a light in a plane through visible points with another inside a sphere; a wide light so low
+                  that visible points lie within qr of its centre (narrow == false); two lights 3e5 and 3e6 units away
+                  (area_beyond_tangent's 1e6 bound); a light below the floor in a scene scaled by 1e-3; a scene scaled
+                  by 1e3 with a second light of zero size
+      umbra       at most 8 nodes: sheared and rotated ellipsoids large against the light (area_in_umbra), a sphere of
+                  radius ~10 (|w| ~ r (1 + 1e-6) on its own surface), a tiny one ~1e3 radii from the floor under it, low
+                  lights whose corners straddle the tangent planes of visible points
+
+    -> (Pair, camera spec, max_depth, family)."""
+    rng = np.random.default_rng(70_000 + seed)
+    cat, k = AREA_MIX[seed % len(AREA_MIX)], (seed // len(AREA_MIX)) % 8
+    G, kinds, cp, glass = MIX_ATTRS[cat][k]
+    if cat == "general":
+        return _mix_general(seed, k, kinds, cp, glass)
+    P = Pair()
+    M = P.M
+    depth, S = 3, 1.0
+    spec = _mix_camera(rng)
+    if isinstance(kinds, int):
+        kinds = _draw_kinds(rng, kinds)
+    n_area = kinds.count("A")
+    if cat == "nodes":
+        areas = [_area_above(rng, lv, (3.0, 6.0)) for lv in _mix_levels(rng, n_area)]
+        total = MIX_NODE_COUNTS[k]
+        P.obj("plane", M.identity(), (0.1, 0.7, 0.3, SHININESS, 0.3, 0.0, 1.0),
+              P.pat("gradient", a=P.pat("solid", _color(rng)), b=P.pat("solid", _color(rng))) if cp else _color(rng))
+        if total % 2:  # a wall behind the scene
+            P.obj("plane", _mul(M, M.rotate("x", math.pi / 2), M.translate(0.0, 0.0, float(rng.uniform(8, 12)))),
+                  _material(rng), _color(rng))
+        n = total - 1 - total % 2
+        head, tail = min(3, n), min(6, max(n - 3, 0))
+        for i in range(n):
+            if i < head or i >= n - tail:  # capsule-rule occluders: the first nodes and the last
+                r = _logu(rng, 0.2, 0.9)
+                c = _capsule_point(rng, areas[i % n_area], r)
+                c[1] = max(c[1], 0.3 * r)
+                if i == 0:  # a large one on the visible floor
+                    r = float(rng.uniform(0.9, 1.5))
+                    c = np.array([rng.uniform(-2, 2), 0.7 * r, rng.uniform(1, 4)])
+            else:  # clutter that shadows a little
+                r = _logu(rng, 0.03, 0.2)
+                c = np.array([rng.uniform(-5, 5), rng.uniform(0.0, 3.0), rng.uniform(-2, 8)])
+            m7, col = _material(rng, 0.3), _color(rng)
+            if i == 0 and k == MIX_BLACK_SURFACE:
+                m7, col = (m7[0], m7[1], 0.0, SHININESS, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0)
+            P.obj("sphere", _mul(M, M.scale(r, r, r), M.translate(*[float(x) for x in c])), m7, col)
+        _add_lights(P, rng, kinds, areas, k)
+    elif cat in ("lights", "levels", "patterns", "glass"):
+        if cat == "levels":
+            levels = [MIX_LEVELS[k]]
+        else:
+            levels = _mix_levels(rng, n_area)
+        areas = [_area_above(rng, lv) for lv in levels]
+        if cat == "glass":
+            depth = 4
+        _mix_content(P, rng, areas, G, int(rng.integers(4, 10)), k, cp=bool(cp), glass=bool(glass),
+                     patterned=cat == "patterns")
+        _add_lights(P, rng, kinds, areas, k)
+    elif cat == "degenerate":
+        S = {6: 1e-3, 7: 1e3}.get(k, 1.0)
+        spec = _mix_camera(rng, S)
+        lv = int(rng.integers(2, 6))
+        a = _area_above(rng, lv, S=S)
+        if k == 0:
+            areas = [_Area(a.corner, a.u, (0.0, 0.0, 0.0), lv)]
+        elif k == 1:
+            areas = [_Area(a.corner, a.u, a.u * float(rng.choice([0.5, -1.0, 2.0])), lv)]
+        elif k == 2:  # crosses the floor: corners on both sides of its plane
+            areas = [_Area((float(rng.uniform(-2, 2)), -1.0, float(rng.uniform(1, 4))), (1.5, 0.0, 0.5), (0.0, 3.0, 0.3), lv)]
+        elif k == 3:  # in a plane through visible points, the second inside a sphere: both set below, from the first occluder
+            areas = [None, None]
+        elif k == 4:  # wide and low, over the visible floor: points within qr of its centre
+            areas = [_Area((-3.0, float(rng.uniform(0.4, 1.0)), -1.0), (6.0, 0.0, 0.0), (0.0, 0.0, 6.0), lv)]
+        elif k == 5:  # on both sides of area_beyond_tangent's light-distance bound
+            d1, d2 = _unit(rng), _unit(rng)
+            d1[1], d2[1] = abs(d1[1]) + 0.5, abs(d2[1]) + 0.5
+            areas = [_Area(d1 * 3e5, (2e4, 0.0, 0.0), (0.0, 0.0, 2e4), lv), _Area(d2 * 3e6, (0.0, 2e5, 0.0), (2e5, 0.0, 0.0), lv + 1)]
+        elif k == 6:  # below the floor
+            areas = [_Area(np.array([rng.uniform(-2, 2), -3.0, rng.uniform(0, 4)]) * S, (2.0 * S, 0.0, 0.0), (0.0, 0.0, 2.0 * S), lv)]
+        else:  # scaled by 1e3; the second light has no size at all
+            areas = [a, _Area(a.qc + np.array([3.0, 1.0, -2.0]) * S, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), lv + 1)]
+        aim = [x for x in areas if x is not None and x.qc[1] > 0.0 and np.linalg.norm(x.qc) < 1e5 * S] or \
+            [_area_above(rng, lv, S=S)]
+        n = int(rng.integers(3, 6))
+        _mix_content(P, rng, aim, 0, n, k, S=S)
+        if k == 3:  # the first occluder (object 1: the floor is object 0) is a large sphere on the floor
+            tr = np.array(P.b.transform[16:32]).reshape(4, 4)
+            # beside it in the horizontal plane through its centre: the plane holds the sphere's visible equator, floor
+            # points see the light from the front (in the floor's own plane every floor sample would have it behind)
+            areas[0] = _Area(tr[:3, 3] + np.array([1.2 * tr[0, 0], 0.0, -1.0]), (2.0, 0.0, 0.0), (0.0, 0.0, 2.5), lv)
+            areas[1] = _Area(tr[:3, 3] - 0.1 * tr[0, 0], (0.2 * tr[0, 0], 0.0, 0.0), (0.0, 0.2 * tr[0, 0], 0.0), lv + 1)
+        _add_lights(P, rng, kinds, areas, k, S)
+    else:  # umbra
+        low = k % 2 == 1  # a low light at the side: its corners straddle the tangent planes of the ellipsoids' tops
+        size = float(rng.choice([0.5, 1.0, 2.0]))
+        if low:
+            centre = np.array([rng.uniform(-7, 7), rng.uniform(1.0, 2.5), rng.uniform(-2, 6)])
+            u, v = np.array([0.0, size, 0.0]), _unit(rng) * size
+        else:
+            centre = np.array([rng.uniform(-4, 4), rng.uniform(6, 10), rng.uniform(-4, 6)])
+            u, v = np.array([size, 0.0, 0.0]), np.array([0.0, 0.0, size * rng.uniform(0.5, 1.0)])
+        areas = [_Area(centre - 0.5 * u - 0.5 * v, u, v, lv) for lv in _mix_levels(rng, n_area)]
+        if n_area == 2:
+            areas[1] = _area_above(rng, areas[1].level, (0.3,))
+        P.obj("plane", M.identity(), (0.1, 0.7, 0.3, SHININESS, 0.3, 0.0, 1.0), _color(rng))
+        for i in range(int(rng.integers(4, 6))):  # ellipsoids between the visible floor and the light
+            fp = np.array([rng.uniform(-3, 3), 0.0, rng.uniform(0, 5)])
+            r = float(rng.uniform(0.9, 1.8))
+            c = fp + (areas[0].qc - fp) / np.linalg.norm(areas[0].qc - fp) * r * rng.uniform(1.1, 2.0)
+            c[1] = max(c[1], 0.8 * r)
+            tr = _mul(M, M.scale(r * rng.uniform(0.75, 1.3), r, r * rng.uniform(0.75, 1.3)), _rot(M, rng),
+                      M.shear(*[float(x) for x in rng.uniform(-0.25, 0.25, 6) * (i % 2)]), M.translate(*[float(x) for x in c]))
+            m7, col = _material(rng, 0.4), _color(rng)
+            if i == 0 and k == MIX_BLACK_SURFACE:
+                m7, col = (m7[0], m7[1], 0.0, SHININESS, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0)
+            P.obj("sphere", tr, m7, col)
+        r = float(rng.uniform(6.0, 14.0))  # over points on it are r (1 + ~1e-6) from its centre
+        P.obj("sphere", _mul(M, M.scale(r, r, r), M.translate(float(rng.uniform(-8, 8)), float(r * rng.uniform(-0.6, 0.2)),
+                                                               float(8.0 + r))), _material(rng, 0.4), _color(rng))
+        fp = np.array([rng.uniform(-2, 2), 0.0, rng.uniform(0, 4)])  # ~1e3 radii above a visible floor point
+        d = (areas[0].qc - fp) / np.linalg.norm(areas[0].qc - fp)
+        r = float(rng.uniform(0.002, 0.006))
+        P.obj("sphere", _mul(M, M.scale(r, r, r), M.translate(*[float(x) for x in fp + d * r * float(rng.uniform(600, 1400))])),
+              _material(rng, 0.4), _color(rng))
+        _add_lights(P, rng, kinds, areas, k)
+    P.log.append(f"camera from={spec['from_']} to={spec['to']} fov={spec['fov']} depth={depth}")
+    return P, spec, depth, cat
+
+
+def _mix_general(seed, k, kinds, cp, glass):
+    """build_area_mix's `general` family: build_general's content by (complex pattern, transparent) — cones or tori, CSG
+    with its glass sphere, patterns or textures, mixed — then a plane inside a group, a glass sphere or a gradient sphere
+    where the content may have drawn none, a mirror sphere, and the lights above the content"""
+    family = {(0, 0): "cones" if k < 2 else "tori", (0, 1): "csg", (1, 0): "patterns" if k < 4 else "textures",
+              (1, 1): "mixed"}[(cp, glass)]
+
+    def lights(P, rng, s):
+        M = P.M
+        g = P.obj("group", M.translate(0.0, 0.0, 12.0 * s))
+        P.obj("plane", M.rotate("x", math.pi / 2), _material(rng), _color(rng), parent=g)
+        extra = [(0.1, 0.5, 0.8, SHININESS, 0.6, 0.0, 1.0)]
+        if glass:
+            extra.append((0.1, 0.4, 0.9, SHININESS, 0.1, 0.9, 1.5))
+        for m7 in extra:
+            r = s * float(rng.uniform(0.5, 1.0))
+            col = P.pat("gradient", a=P.pat("solid", _color(rng)), b=P.pat("solid", _color(rng))) if cp else _color(rng)
+            P.obj("sphere", _mul(M, M.scale(r, r, r), M.translate(*[float(x) for x in rng.uniform(-3, 3, 3) * [s, 0.3 * s, s]])),
+                  m7, col)
+        areas = []
+        for lv in _mix_levels(rng, kinds.count("A")):
+            a = _area_above(rng, lv, (6.0, 9.0), S=s)
+            areas.append(_Area(a.corner + np.array([0.0, 1.0 * s, 0.0]), a.u, a.v, lv))
+        _add_lights(P, rng, kinds, areas, k, s, points=[np.array([rng.uniform(-8, 8), rng.uniform(-2, 3), rng.uniform(4, 10)]) * s
+                                                         for _ in range(kinds.count("p"))])
+        if k == MIX_BLACK_SURFACE:
+            P.obj("sphere", _mul(M, M.scale(1.2 * s, 1.2 * s, 1.2 * s), M.translate(0.0, -1.0 * s, -2.0 * s)),
+                  (0.1, 0.7, 0.0, SHININESS, 0.0, 0.0, 1.0), (0.0, 0.0, 0.0))
+
+    P, spec, depth, _ = build_general(seed, light=lights, family=family, rng_base=71_000)
+    return P, spec, depth, "general"
+
+
+def mix_key(P, depth):
+    """The kernel a frame of this scene takes, from the builder's descriptor alone as traits() reads it, extended by
+    complex patterns and the lights: (G, PRE, CP, family at this depth, AR) — render.hip launch_level (G),
+    render_levels.inc (PRE: at most PRELIT_LIGHTS lights; CP: flatten.cpp complex_patterns), frame_plan.hpp family_of."""
+    import rray_amd as R
+
+    L = R._lib
+    t = traits(P)
+    g = 2 if t["general"] else 1 if t["groups"] else 0
+    cp = any(kd in (L.PAT["gradient"], L.PAT["blend"]) or kd >= L.PAT["perturbed"] for kd in P.b.pat_kind)
+    family = "Tree" if t["transparent"] else "Chain" if t["reflective"] and depth > 0 else "Level0"
+    return g, int(t["lights"] <= PRELIT_LIGHTS), int(cp), family, int(t["area"])
+
+
+def light_kinds(P):
+    """the scene's lights in order: "A" area, "p" point"""
+    import rray_amd as R
+
+    return "".join("A" if kd == R._lib.LIGHT_AREA else "p" for kd in P.b.light_kind)
 
 
 def cameras(P, spec, W, H):
@@ -617,10 +1003,16 @@ def cameras(P, spec, W, H):
 # --- the production dispatch paths (tests/test_gpu_fuzz_paths.py, tests/test_fuzz_paths_host.py) -------------------
 
 BUILDERS = {"build": build, "general": build_general, "area": build_area, "own": build_own}
+# build_path's names: the mix is a list of its own (MIX_PATH_SCENES) and stays out of BUILDERS, which the mode x builder
+# table of tests/test_gpu_fuzz_paths.py iterates and whose 48 PATH_SCENES stay as they are
+PATH_BUILDERS = dict(BUILDERS, mix=build_area_mix)
 # the first two seeds of every category of every builder: 8, 6, 4 and 6 categories
 PATH_SCENES = ([("build", s) for s in range(16)] + [("general", s) for s in range(12)] +
                [("area", s) for s in range(8)] + [("own", s) for s in range(12)])
 PATH_IDS = [f"{b}-{s}" for b, s in PATH_SCENES]
+# the area-light mix through the same modes, a list of its own: the first two seeds of every family of build_area_mix
+MIX_PATH_SCENES = [("mix", s) for s in range(16)]
+MIX_PATH_IDS = [f"{b}-{s}" for b, s in MIX_PATH_SCENES]
 PRELIT_LIGHTS = 2  # kernels.hpp RR_PRELIT_LIGHTS: the resident tile loop's kernel holds at most two lights' terms
 QUERY_SIZE = (33, 17)  # the query batch's camera: partial tiles on both edges
 QUERY_PREFIXES = (1, 63, 65, 257)
@@ -628,7 +1020,7 @@ QUERY_PREFIXES = (1, 63, 65, 257)
 
 def build_path(name, seed):
     """-> (Pair, camera spec, max_depth, category, jitter seed) of one PATH_SCENES entry"""
-    P, spec, depth, cat = BUILDERS[name](seed)
+    P, spec, depth, cat = PATH_BUILDERS[name](seed)
     return P, spec, depth, cat, seed
 
 

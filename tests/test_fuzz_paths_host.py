@@ -151,7 +151,7 @@ if __name__ == "__main__":
     import sys
 
     sys.path.insert(0, ROOT)
-    out = {}
+    out = json.load(open(THRESHOLDS))  # other lists' keys stay (mix-*: tests/test_area_mix_host.py)
     for scene in F.PATH_SCENES:
         thr, frac, colours = threshold_of(*scene)
         assert (thr is None and scene in ONE_COLOUR) or math.isfinite(thr), scene

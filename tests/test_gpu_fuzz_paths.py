@@ -28,6 +28,10 @@ DESIGN.md §3.2) by scene_fuzz.check_frame — the canvas bit for bit, rays / sh
                bit for bit, and on prefixes of 1, 63, 65 and 257 rays.  Both sides key an area light's jitter by the
                ray's index in the batch (Oracle.set_context per ray)
 
+scene_fuzz.MIX_PATH_SCENES (16 scenes: the first two seeds of every family of build_area_mix — two area lights, lights
+of every order, general shapes, patterns, glass, degenerate light geometry, umbrae) go through the same six modes as a
+list of their own (the test_mix_* tests below), with thresholds under the keys mix-0 .. mix-15.
+
 The kernel names of rr_kernel_times do not tell the tree kernel from the chain kernel: both count as `chain`.  The last
 test prints mode x builder x (scenes, launches per kernel, loop or per-tile frames) and asserts no row is empty."""
 import collections
@@ -322,6 +326,53 @@ def test_query_batches(R, renderer, name, seed):
         raise
     finally:
         P.o.set_pow_mode(0)
+
+
+# --- the area-light mix (scene_fuzz.MIX_PATH_SCENES: the first two seeds of every family of build_area_mix) through
+# the same six modes: the mode functions above, scene by scene
+
+MIX_SCENES = pytest.mark.parametrize("name,seed", F.MIX_PATH_SCENES, ids=F.MIX_PATH_IDS)
+
+
+@MIX_SCENES
+def test_mix_depth0_fused_level0(R, renderer, name, seed):
+    test_depth0_fused_level0(R, renderer, name, seed)
+
+
+@MIX_SCENES
+def test_mix_aa3_pixel_waves(R, renderer, name, seed):
+    t = F.traits(F.build_path(name, seed)[0])
+    assert t["reflective"] or t["transparent"]  # every scene of the mix has a mirror floor
+    test_aa3_pixel_waves(R, renderer, name, seed)
+
+
+@MIX_SCENES
+def test_mix_ragged_frames(R, renderer, name, seed):
+    test_ragged_frames(R, renderer, name, seed)
+
+
+@MIX_SCENES
+def test_mix_bands_and_parts(R, renderer, name, seed):
+    test_bands_and_parts(R, renderer, name, seed)
+
+
+@MIX_SCENES
+def test_mix_listed_pixels(R, renderer, name, seed):
+    assert json.load(open(THRESHOLDS))[f"{name}-{seed}"] is not None  # no frame of the mix holds one colour
+    test_listed_pixels(R, renderer, name, seed)
+
+
+@MIX_SCENES
+def test_mix_query_batches(R, renderer, name, seed):
+    test_query_batches(R, renderer, name, seed)
+
+
+def test_every_mode_saw_the_mix():
+    """mode x the mix: every mode recorded all 16 scenes, area lights in every one"""
+    for mode in MODES:
+        row = TABLE.get((mode, "mix"))
+        assert row is not None and len(row["scenes"]) == len(F.MIX_PATH_SCENES), (mode, row)
+        print(f"{mode:<10} mix      {len(row['scenes']):>6}  " + " ".join(f"{k}={v}" for k, v in sorted(row["launches"].items())))
 
 
 def test_every_mode_saw_every_builder():
