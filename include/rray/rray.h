@@ -347,6 +347,36 @@ int rr_render_adaptive(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* 
 int rr_render_adaptive_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, double threshold,
                               void* d_avg, void* d_mask, void* d_n_refined, void* hip_stream);
 
+/* ---- batches of views (additive to ABI 11; test RR_HAS_VIEWS) ----
+ * Many cameras of the uploaded scene in one call: stereo pairs, cube-map faces, turntables, light fields, training
+ * sets.  `cams` is a host array of n_views cameras that share hsize and vsize (each has its own transform, field of
+ * view and derived fields); it is read before the call returns.  `opts` holds for the whole batch (aa, max_depth,
+ * seed, jitter_mode, flags).  An output is requested by its flag and then needs its buffer: RR_OUT_AVG n_views x H x W
+ * x 3 doubles, RR_OUT_CANVAS n_views x vsize x hsize x 3 doubles; view k is slice k of each, so a caller can wrap
+ * either as one tensor.  An unrequested output's pointer is ignored.
+ * Definition: slice k is what rr_render(ctx, &cams[k], opts, ...) writes, bit for bit — area lights included: a
+ * sample's jitter identity is py * hsize + px within its own view, so a view does not depend on its place in the
+ * batch.
+ * The batch runs in passes of whole views (as many as fit one pass of the context, 2^27 samples unless RRAY_BATCH
+ * says otherwise), each pass one launch of the scene's kernel family; a view's samples take whole 64-lane waves.
+ * The call leaves the context's single-frame state alone (cached camera bundles, tile order): an rr_render before
+ * and after it returns the same image and the same counters.  rr_resident_launch after a batch reports 0 / 0.
+ * rr_last_stats / stats afterwards: rays, shadow_rays, shade_events, n1n2_scans, samples and nan_rays are the sums of
+ * the single frames' values; prim_tests, exact_flops and wave_visits are reproducible but may differ from those sums
+ * (the culling bundles differ); kernel_ms is one event pair around the batch (0 with RR_NO_FRAME_TIMING).
+ * n_views == 0: RR_OK, nothing written.  RR_E_ARG: a null ctx / cams / opts, n_views < 0, a requested output with a
+ * null pointer, cameras of differing sizes, sizes inconsistent with aa, part != 0, nparts != 1, a row band,
+ * RR_OUT_AVG_F32, RR_PART_INTERLEAVE, a multi-device or virtual context, the RRAY_UNFUSED / RRAY_NO_TREE /
+ * RRAY_NO_CHAIN per-level paths.  RR_E_LIMIT: one view holds more samples than one pass (render it with rr_render).
+ * Other errors are rr_render's; RR_E_NAN is returned after the outputs are written.
+ * rr_render_views: host buffers, blocking.  rr_render_views_device: device buffers on the context's device,
+ * everything enqueued on `hip_stream` (NULL: ctx stream) and NOT synchronised. */
+#define RR_HAS_VIEWS 1
+int rr_render_views(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const rr_render_opts* opts,
+                    double* out_canvas, double* out_avg, rr_stats* stats);
+int rr_render_views_device(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const rr_render_opts* opts,
+                           void* d_canvas, void* d_avg, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

@@ -48,7 +48,14 @@ for _u in LISTED_UNITS:
     _like = _u.replace("render_listed_", "render_")
     if _like in UNIT_FLAGS:
         UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+# batches of views (render_views.hip, rr_render_views): the same kernels once more with the camera-table level-0 source
+# (RR_VIEWS, namespace rr::views), each built like the unit it mirrors
+VIEWS_UNITS = [f"render_views_{k}_g{g}_{lc}.hip" for k in ("chain", "tree", "levels") for g in (2, 1, 0) for lc in ("lds", "gl")]
+for _u in VIEWS_UNITS:
+    _like = _u.replace("render_views_", "render_")
+    if _like in UNIT_FLAGS:
+        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
+SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 
@@ -146,7 +153,7 @@ def _resources(stderr):
 
 def cross_lane_kernel(demangled):
     """device_core.inc cross_lane_ok: kernels whose walks read other lanes' registers (v_readlane)."""
-    m = re.search(r"rr::(?:listed::)?(shade_kernel|persist_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
+    m = re.search(r"rr::(?:listed::|views::)?(shade_kernel|persist_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
                   demangled)
     if not m:
         return False

@@ -84,6 +84,10 @@ struct rr_ctx {
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
+    // batches of views (rr_render_views_device): the camera table on the device, and the host copy it is filled from
+    // (the caller's array is read before the call returns)
+    DBuf views;
+    std::vector<rr::DevView> views_host;
     // per-tile camera-ray bundles of the last camera / part layout (tile_bundle_kernel), reused while they match
     DBuf tiles;
     struct TileKey {
@@ -426,6 +430,10 @@ rr::FramePlan plan_run(const rr_ctx* c, const FrameFacts& facts, const rr::Level
     r.batch = c->batch;
     r.queue_budget = c->queue_budget;
     r.zero_next = c->zero_next;
+    if (A.views) {
+        r.view_e = A.view_e;
+        r.views = (int32_t)(total / A.view_e);
+    }
     return rr::plan_frame(facts.traits, facts.sw, r);
 }
 
@@ -559,6 +567,13 @@ rr::LevelArgs level_args(rr_ctx* c, const rr::LevelArgs& base_args, const rr::Fr
     if (plan.order.ok && d == 0) order_level0_args(c, plan, A);
     A.counters = frame_counters(c, c->epoch);
     A.counters_zero = (c->zero_next && d == 0 && base == 0) ? frame_counters(c, c->epoch ^ 1) : nullptr;
+    if (base_args.views) {  // a pass of whole views: the events, the camera table and the outputs start at its first view
+        const int64_t v0 = base / base_args.view_e, vsamples = base_args.hs * base_args.lrows;
+        A.base = 0;
+        A.views = base_args.views + v0;
+        if (A.out) A.out += 3 * v0 * vsamples;
+        if (A.avg) A.avg = static_cast<double*>(A.avg) + 3 * v0 * (vsamples / ((int64_t)A.aa * A.aa));
+    }
     return A;
 }
 
@@ -600,6 +615,18 @@ hipError_t launch_level0_frame(rr_ctx* c, const rr::FramePlan& plan, rr::LevelAr
 
 hipError_t launch_family(rr_ctx* c, const rr::FramePlan& plan, rr::LevelArgs& A, hipStream_t st) {
     const bool listed = A.list != nullptr;  // the plan admits the in-wave families only
+    if (A.views) {  // a batch of views: the plan admits the in-wave families only
+        switch (plan.family) {
+            case rr::Family::Tree:
+                return rr::launch_tree_views(c->S, A, st, kprof(c));
+            case rr::Family::Chain:
+                return rr::launch_chain_views(c->S, A, st, kprof(c));
+            case rr::Family::Level0:
+                return rr::launch_level_views(c->S, A, st, kprof(c));
+            default:
+                return hipErrorInvalidValue;
+        }
+    }
     switch (plan.family) {
         case rr::Family::Tree:
             return listed ? rr::launch_tree_listed(c->S, A, st, kprof(c)) : rr::launch_tree(c->S, A, st, kprof(c));
@@ -874,7 +901,7 @@ void rr_destroy(rr_ctx* c) {
     for (DBuf* b : {&c->culls, &c->inner, &c->chunks, &c->nodes, &c->groups, &c->shapes, &c->tris, &c->mats, &c->pats, &c->lights, &c->textures, &c->texels, &c->counters,
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
-                    &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask})
+                    &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -1624,6 +1651,126 @@ int rr_render_adaptive(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o,
     HIPCHK(hipMemcpyAsync(&n, mbase, sizeof n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (n_refined) *n_refined = n;
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
+}
+
+// ---- batches of views (render_views.hip) ----
+// what both entry points refuse before they look at the context (so a host without a device can test it)
+static int views_check_args(const rr_camera* cams, int32_t n_views, const rr_render_opts* o, const void* canvas,
+                            const void* avg) {
+    if (!cams) return fail(RR_E_ARG, "rr_render_views: null camera array");
+    if (!o) return fail(RR_E_ARG, "rr_render_views: null options");
+    if (n_views < 0) return fail(RR_E_ARG, "rr_render_views: n_views is negative");
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "batches of views are whole frames: part 0 of 1, no band");
+    if (o->flags & RR_OUT_AVG_F32) return fail(RR_E_ARG, "batches of views write f64 images: RR_OUT_AVG_F32 is not served");
+    if (o->flags & RR_PART_INTERLEAVE)
+        return fail(RR_E_ARG, "batches of views run on one device: RR_PART_INTERLEAVE is not served");
+    if ((o->flags & RR_OUT_CANVAS) && !canvas) return fail(RR_E_ARG, "rr_render_views: RR_OUT_CANVAS with a null canvas buffer");
+    if ((o->flags & RR_OUT_AVG) && !avg) return fail(RR_E_ARG, "rr_render_views: RR_OUT_AVG with a null image buffer");
+    for (int32_t k = 1; k < n_views; ++k)
+        if (cams[k].hsize != cams[0].hsize || cams[k].vsize != cams[0].vsize)
+            return fail(RR_E_ARG, "the cameras of a batch must share hsize and vsize: camera " + std::to_string(k) + " is " +
+                                      std::to_string(cams[k].hsize) + "x" + std::to_string(cams[k].vsize) + ", camera 0 " +
+                                      std::to_string(cams[0].hsize) + "x" + std::to_string(cams[0].vsize));
+    return RR_OK;
+}
+
+int rr_render_views_device(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_render_opts* o, void* d_canvas,
+                           void* d_avg, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = views_check_args(cams, n_views, o, d_canvas, d_avg);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "batches of views need a single-device context (no multi-device or virtual context)");
+    if (n_views == 0) return RR_OK;
+    rc = rr::render_validate(c, &cams[0], o);  // rr_render's own checks (scene, depth, sizes against aa)
+    if (rc != RR_OK) return rc;
+    const int32_t aa = o->aa;
+    const int64_t hs = cams[0].hsize, vs = cams[0].vsize, W = hs / aa, H = vs / aa;
+    const int64_t E = rr::view_events(hs, vs), total = (int64_t)n_views * E;
+    const FrameFacts facts = frame_facts(c, o->max_depth);
+    double* canvas = (o->flags & RR_OUT_CANVAS) ? static_cast<double*>(d_canvas) : nullptr;
+    double* avg = (o->flags & RR_OUT_AVG) ? static_cast<double*>(d_avg) : nullptr;
+    // as rr_render_device's frames: aa 1 and the level-0 waves' own average (aa 2 / 4 / 8, full tiles) write the image
+    // directly; every other aa goes through the stacked canvases, n_views * vs rows of hs samples, which aa_kernel
+    // averages as one image (vs = H * aa: no pixel's box crosses a view).  Pixel waves do not serve batches.
+    rr::OutputPlan mode = rr::plan_output(facts.traits, facts.sw, avg != nullptr, aa, hs, vs, o->max_depth, 8, c->batch);
+    mode.pw = false;
+    mode.direct_avg = avg && (aa == 1 || mode.wave_avg);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->views.ensure(((size_t)n_views + rr::RR_VIEW_TABLE_PAD) * sizeof(rr::DevView)));
+    rr::LevelArgs A = camera_args(&cams[0], o, aa, 0, 8);  // part 0 of 1 (views_check_args); A.cam itself is not read
+    A.lrows = vs;
+    A.views = c->views.as<rr::DevView>();
+    A.view_e = (uint32_t)std::min<int64_t>(E, (int64_t)1 << 31);
+    {  // what the plan refuses (a per-level family, a view larger than a pass), before anything is enqueued
+        const FrameOut o0{canvas, mode.direct_avg ? avg : nullptr, 0, mode.wave_avg ? aa : 0, nullptr};
+        const rr::FramePlan pre = plan_run(c, facts, A, total, o->max_depth, o0);
+        if (pre.err != RR_OK) return fail(pre.err, pre.msg);
+    }
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    if (!canvas && avg && !mode.direct_avg) {
+        HIPCHK(c->canvas.ensure((size_t)n_views * hs * vs * 3 * sizeof(double)));
+        canvas = c->canvas.as<double>();
+    }
+    // the camera table: the context's host copy (the caller's array is free after this call), then its device buffer,
+    // on the render's stream
+    c->views_host.assign((size_t)n_views + rr::RR_VIEW_TABLE_PAD, rr::DevView{});
+    for (int32_t k = 0; k < n_views; ++k) {
+        rr::LevelArgs T{};
+        set_camera(T, &cams[k]);
+        c->views_host[k].cam = T.cam;
+        c->views_host[k].affine = T.cam_affine;
+    }
+    HIPCHK(hipMemcpyAsync(c->views.p, c->views_host.data(), c->views_host.size() * sizeof(rr::DevView),
+                          hipMemcpyHostToDevice, st));
+    c->frame_timed = !(o->flags & RR_NO_FRAME_TIMING);
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e0, st));
+    // the colour frames' per-camera state stays as it is: no cached bundles, no cost order, no resident launch
+    begin_frame_counters(c);
+    rc = run_levels(c, facts, A, total, o->max_depth, canvas, st, mode.direct_avg ? avg : nullptr, 0,
+                    mode.wave_avg ? aa : 0, nullptr);
+    c->zero_next = false;
+    if (rc != RR_OK) return rc;
+    if (avg && !mode.direct_avg) HIPCHK(rr::launch_aa(canvas, avg, W, (int64_t)n_views * H, aa, st, kprof(c)));
+    end_frame_counters(c);
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    c->stats_pending = true;
+    c->last.samples = (uint64_t)n_views * (uint64_t)(hs * vs);
+    c->adapt_pending = false;
+    return RR_OK;
+}
+
+int rr_render_views(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_render_opts* o, double* out_canvas,
+                    double* out_avg, rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = views_check_args(cams, n_views, o, out_canvas, out_avg);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "batches of views need a single-device context (no multi-device or virtual context)");
+    if (n_views == 0) return RR_OK;
+    rc = check_opts(&cams[0], o);
+    if (rc != RR_OK) return rc;
+    const int64_t hs = cams[0].hsize, vs = cams[0].vsize, W = hs / o->aa, H = vs / o->aa;
+    const size_t img = (size_t)n_views * W * H * 3 * sizeof(double), cnv = (size_t)n_views * hs * vs * 3 * sizeof(double);
+    const bool want_avg = (o->flags & RR_OUT_AVG) != 0, want_canvas = (o->flags & RR_OUT_CANVAS) != 0;
+    HIPCHK(hipSetDevice(c->device));
+    if (want_avg) HIPCHK(c->qout.ensure(img));
+    if (want_canvas) HIPCHK(c->canvas.ensure(cnv));
+    rc = rr_render_views_device(c, cams, n_views, o, want_canvas ? c->canvas.p : nullptr, want_avg ? c->qout.p : nullptr,
+                                nullptr);
+    if (rc != RR_OK) return rc;
+    if (want_canvas) HIPCHK(hipMemcpyAsync(out_canvas, c->canvas.p, cnv, hipMemcpyDeviceToHost, c->stream));
+    if (want_avg) HIPCHK(hipMemcpyAsync(out_avg, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     rr_stats local;
     rc = rr_last_stats(c, stats ? stats : &local);
     if (rc != RR_OK) return rc;

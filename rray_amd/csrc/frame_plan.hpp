@@ -129,7 +129,14 @@ struct FrameRequest {
     int64_t batch;
     size_t queue_budget;
     bool zero_next;  // the frame's first run: its first launch clears the next frame's counters
+    // a batch of views (rr_render_views): `views` cameras of hs x lrows samples each, every view view_e =
+    // view_events(hs, lrows) level-0 events (total = views * view_e).  0: a single frame.  Last, value-initialised.
+    int32_t views{};
+    int64_t view_e{};
 };
+
+// level-0 events of one view of a batch: its samples rounded up to whole waves, so a wave never holds two views
+inline int64_t view_events(int64_t hs, int64_t lrows) { return (hs * lrows + 63) / 64 * 64; }
 
 struct FramePlan {
     Family family;
@@ -152,6 +159,7 @@ struct FramePlan {
     } order;
     int64_t pw_n;     // pixel waves: the launch's events, whole waves of 64 lanes
     bool persist_candidate;  // all the persistent loop asks of a frame but rr::persist_plan's own answer
+    int64_t views_per_pass;  // a batch of views: whole views per pass (B = views_per_pass * view_e), else 0
     int err;          // RR_OK, or the code and text the run fails with
     const char* msg;
 };
@@ -195,6 +203,31 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
         f.msg = "internal: the listed-pixel pass needs one batch of a production kernel family";
         return f;
     }
+    // a batch of views: passes of whole views through the in-wave kernels, one launch each.  No per-camera state of
+    // the context serves it: no cached bundles, no cost order, no resident loop, no deep queue, no pixel waves
+    if (r.views > 0) {
+        if (r.view_e < 64 || r.view_e % 64 != 0 || r.view_e < r.hs * r.lrows || r.total != r.views * r.view_e || r.rays0 ||
+            r.listed || r.pw || r.box_avg) {
+            f.err = RR_E_ARG;
+            f.msg = "internal: a view batch is whole views of whole waves from camera rays";
+            return f;
+        }
+        if (!one_level) {
+            f.err = RR_E_ARG;
+            f.msg = "batches of views are not served by the per-level paths (RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN)";
+            return f;
+        }
+        // a pass's samples are indexed in 32 bits, as a part's
+        const int64_t pass_cap = std::min<int64_t>(r.batch, ((int64_t)1 << 31) - 64);
+        if (r.view_e > pass_cap) {
+            f.err = RR_E_LIMIT;
+            f.msg = "one view's samples must fit one pass of the context (render such a view with rr_render)";
+            return f;
+        }
+        f.views_per_pass = std::min<int64_t>(pass_cap / r.view_e, r.views);
+        f.B = f.views_per_pass * r.view_e;
+        f.passes = false;
+    }
     f.P = plan_levels(f.B, f.k, f.plan_depth, f.ext, f.fused);
     if (f.P.max_cap >= ((int64_t)1 << 31)) {
         f.err = RR_E_LIMIT;
@@ -211,11 +244,11 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
     // tiles per wave (C3 10.54 -> 8.98 ms with the blocks); the area-light scenes' block-wide sample dealing
     // prefers packed waves (C5 2.27 vs 2.30 ms)
     f.pad_children = f.fused && !t.has_area;
-    f.tile_fast = full_tiles(r.rays0, r.hs, r.lrows, 0);
+    f.tile_fast = full_tiles(r.rays0, r.hs, r.lrows, 0);  // a batch of views: of each view
     // deep chains: frames whose samples are delivered one by one (not the in-wave AA average).  Opt-in: on C3 the
     // deep launch took 1.85 ms for what the camera waves did in 1.54 — the deep rays' walks are latency-bound
     // whether their waves are full or not
-    f.spill = f.family == Family::Chain && r.aa_wave == 0 && !r.pw && !r.listed && r.max_depth >= RR_DEEP_FROM && sw.deep;
+    f.spill = f.family == Family::Chain && r.aa_wave == 0 && !r.pw && !r.listed && r.views == 0 && r.max_depth >= RR_DEEP_FROM && sw.deep;
     f.deep_seg_cap = (int64_t)256 << RR_DEEP_SHIFT;
     f.deep_nseg = (((f.B + 255) / 256) + (1 << RR_DEEP_SHIFT) - 1) >> RR_DEEP_SHIFT;
     // cost-ordered level-0 tiles: one-batch frames of full 8x8 tiles whose level 0 is the whole frame (no
@@ -234,7 +267,7 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
     // slots' order entries are their own indices (their lanes are past the launch's samples and do nothing but record
     // a cost nobody sorts)
     f.order.n_pad = (n_tiles + 3) & ~(int64_t)3;
-    f.order.ok = (f.fused || t.tree) && !t.general && f.B >= r.total && n_tiles > 0 && n_tiles < ((int64_t)1 << 31) &&
+    f.order.ok = r.views == 0 && (f.fused || t.tree) && !t.general && f.B >= r.total && n_tiles > 0 && n_tiles < ((int64_t)1 << 31) &&
                  (sw.order_group == 1 || n_tiles % 4 == 0) &&  // the group order permutes a block's four tiles
                  (r.pw || n_tiles * 64 == r.total) &&
                  ((t.has_groups && (f.k == 0 || r.max_depth == 0)) || (chain && !sw.no_chain_order));
@@ -242,7 +275,7 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
     // chain and level-0-only frames of one layout, and each order unit, keep orders of their own
     f.order.pad = (chain ? 1 : 0) | (sw.order_group == 1 ? 2 : 0);
     // a one-level, one-batch frame of full tiles may run as one resident launch
-    f.persist_candidate = f.family == Family::Level0 && !r.listed && f.B >= r.total && f.tile_fast && !r.pw &&
+    f.persist_candidate = f.family == Family::Level0 && !r.listed && r.views == 0 && f.B >= r.total && f.tile_fast && !r.pw &&
                           r.total % 64 == 0 && r.total / 64 < ((int64_t)1 << 31) && r.zero_next;
     return f;
 }

@@ -11,6 +11,17 @@
 
 namespace rr {
 
+// One camera of a batch of views (LevelArgs.views): the camera and whether its inverse's row 3 is (0, 0, 0, 1)
+// (LevelArgs.cam_affine of a single frame).
+struct DevView {
+    DevCamera cam;
+    int32_t affine;
+    int32_t pad;
+};
+// the table's records past the last view: a launch's last block may hold up to three waves past its events, which
+// read their (unused) view's affine flag
+constexpr int RR_VIEW_TABLE_PAD = 4;
+
 // Arguments of one wavefront level (see wavefront.hpp).
 struct LevelArgs {
     DevCamera cam;           // level-0 ray source (when rays0 == nullptr)
@@ -89,6 +100,12 @@ struct LevelArgs {
     // the table behind DevScene.nodes.  Set by their launches (render_levels.inc uniform_hit_on); RRAY_NO_UNIFORM_HIT=1
     // keeps the per-lane code, for tests and same-binary timing.  In the struct's tail padding: no field moves.
     uint32_t uniform_hit;
+    // a batch of views (rr_render_views; the rr::views kernels only, render_views_*.hip): level-0 event i is event
+    // i % view_e of view i / view_e of the pass, view_e = ceil(hs * lrows / 64) * 64 events per view, so a wave holds
+    // samples of one view only and reads that view's camera with a wave-uniform index; hs x lrows is one view's
+    // canvas.  At the struct's end: no other field moves.
+    const DevView* views;
+    uint32_t view_e;
 };
 
 struct CombArgs {
@@ -231,7 +248,23 @@ void launch_tree_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, Ke
 hipError_t launch_level_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
 hipError_t launch_chain_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
 hipError_t launch_tree_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
-// The passes around it, all on the caller's stream with their counts in HBM:
+// Batches of views (rr_render_views): many cameras of one scene in one launch per pass.  The level,
+// chain and tree kernels compiled a third time, in namespace rr::views with RR_VIEWS defined
+// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip): level-0 events come from the camera table LevelArgs.views.
+// The production and listed instantiations do not carry the source.  launch_*_views (render_views.hip) pick the
+// scene's (G, LC) variant as launch_level / launch_chain / launch_tree do.
+namespace views {
+template <int G, bool LC>
+void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
+template <int G, bool LC>
+void launch_chain_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof, bool deep);
+template <int G, bool LC>
+void launch_tree_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
+}  // namespace views
+hipError_t launch_level_views(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+hipError_t launch_chain_views(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+hipError_t launch_tree_views(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
+// The passes around the adaptive refine pass, all on the caller's stream with their counts in HBM:
 //   mask     rule: pixel p is refined iff some q of its clipped 3x3 neighbourhood has !(max_c |F[p][c] - F[q][c]| <= thr);
 //            writes flags (and mask, when not null) and one count per block of RR_ADAPT_BLOCK pixels
 //   scan     exclusive scan of the block counts (in place); n_list = refined pixels, n_events = n_list * aa^2,

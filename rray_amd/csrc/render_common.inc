@@ -108,6 +108,38 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
         return r;
     }
 #endif
+#ifdef RR_VIEWS
+    // A batch of views (the rr::views kernels): event t is event t % view_e of view t / view_e, view_e a multiple of
+    // 64, so the wave's view and its tile within the view are wave-uniform (scalar); hs x lrows is one view's canvas.
+    // Full tiles (tile_fast) take the wave-uniform tile arithmetic, other sizes tile_to_local_u32 within the view, and
+    // events past the view's samples hold none (ok).  lrow counts the rows of the stacked canvases (view * lrows +
+    // the view's row), so ls = lrow * hs + px is the sample's slot in the batch's output and deliver_wave_avg's pixel
+    // arithmetic holds as it is (lrows is a multiple of aa); py is the view's own canvas row, the camera's and the
+    // jitter identity's.
+    {
+        const uint32_t t = (uint32_t)(A.base + i);
+        const uint32_t w = OWN ? (uint32_t)uniform((int)(t >> 6)) : t >> 6;
+        const uint32_t e64 = A.view_e >> 6, view = w / e64, tw = w - view * e64;
+        const uint32_t hs = (uint32_t)A.hs, vs = (uint32_t)A.lrows;
+        const uint32_t lane = OWN ? (uint32_t)lane_id() : t & 63u;
+        bool in = true;
+        if (A.tile_fast) {
+            const uint32_t band = tw / A.tiles_per_row, tc = tw - band * A.tiles_per_row;
+            r.py = band * 8u + (lane >> 3);
+            r.px = tc * 8u + (lane & 7u);
+        } else {
+            const uint32_t tl = tw * 64u + lane;
+            in = tl < hs * vs;
+            const uint32_t l = tile_to_local_u32(in ? tl : 0u, hs, vs);
+            r.py = l / hs;
+            r.px = l - r.py * hs;
+        }
+        if (ok) *ok = in;
+        r.lrow = view * vs + r.py;
+        r.ls = r.lrow * hs + r.px;
+        return r;
+    }
+#else
     const uint32_t hs = (uint32_t)A.hs;
     uint32_t lrow;
     if (PW && A.pw) {  // OWN indexing, one batch (base 0): the wave's slot, or the wave the cost order puts there
@@ -139,6 +171,7 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
     r.py = canvas_row(A, lrow);
     r.lrow = lrow;
     return r;
+#endif
 }
 template <bool OWN, bool ORDER = false>
 __device__ __forceinline__ Px0 level0_px_if(const LevelArgs& A, int64_t i, int64_t tile = -1) {
@@ -172,9 +205,21 @@ __device__ __forceinline__ Ray camera_ray(const DevCamera& C, bool affine, uint3
 
 // level-0 camera rays of full 8x8 tiles through an affine camera: one origin, a planar grid of directions
 // (make_bundle's cam_tile bundle)
+#ifdef RR_VIEWS
+// the view of this wave's launch slot (OWN indexing, as own_tile): wave-uniform, a scalar
+__device__ __forceinline__ uint32_t own_view(const LevelArgs& A) {
+    const uint32_t w = (uint32_t)(A.base >> 6) + blockIdx.x * 4u + ((uint32_t)uniform((int)threadIdx.x) >> 6);
+    return w / (A.view_e >> 6);
+}
+// full tiles of the wave's own view, when its camera is affine (its flag from the camera table: a scalar load)
+__device__ __forceinline__ bool cam_tile(const LevelArgs& A) {
+    return A.level == 0 && !A.rays0 && A.tile_fast && cp(A.views)[own_view(A)].affine != 0;
+}
+#else
 __device__ __forceinline__ bool cam_tile(const LevelArgs& A) {
     return A.level == 0 && !A.rays0 && A.tile_fast && A.cam_affine;
 }
+#endif
 
 // this wave's entry of the per-frame tile-bundle table (level 0, tile_fast, OWN indexing), or null
 template <bool ORDER = false>
@@ -195,7 +240,25 @@ __device__ __forceinline__ Ray event_ray(const LevelArgs& A, int64_t i, const Px
         return {mk(p[0], p[1], p[2]), mk(p[3], p[4], p[5])};
     }
     s0 = (uint64_t)q.py * (uint64_t)A.hs + q.px;
+#ifdef RR_VIEWS
+    // the wave's own camera: the view index is wave-uniform (every rr::views kernel indexes its events by launch
+    // slot), so the record is read through the constant address space into scalar registers, and camera_ray itself is
+    // the single frame's
+    {
+        const uint32_t view = (uint32_t)uniform((int)((uint32_t)(A.base + i) >> 6)) / (A.view_e >> 6);
+        const cptr<DevView> V = cp(A.views) + view;
+        DevCamera C;
+        C.hsize = C.vsize = 0;  // not read by camera_ray
+        C.half_width = V->cam.half_width;
+        C.half_height = V->cam.half_height;
+        C.pixel_size = V->cam.pixel_size;
+        for (int k = 0; k < 16; ++k) C.inv[k] = V->cam.inv[k];
+        for (int k = 0; k < 4; ++k) C.origin[k] = V->cam.origin[k];
+        return camera_ray(C, V->affine != 0, q.px, q.py);
+    }
+#else
     return camera_ray(A.cam, A.cam_affine, q.px, q.py);
+#endif
 }
 template <bool OWN>
 __device__ __forceinline__ Ray event_ray(const LevelArgs& A, int64_t i) {

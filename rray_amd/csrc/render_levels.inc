@@ -839,7 +839,7 @@ void launch_chain_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
     const size_t lds = cull_lds(S) + (pre ? (size_t)S.n_lights * 6 * 256 * sizeof(double) : 0) +
                        (S.has_area ? sizeof(AreaStage) : 0) + sizeof(ChainStage);
     Span s(prof, deep ? K_DEEP : K_CHAIN, st);
-#ifndef RR_LISTED  // listed pixels never leave their camera wave for the deep queue
+#if !defined(RR_LISTED) && !defined(RR_VIEWS)  // listed pixels and batched views never leave their camera wave for the deep queue
     if (deep)
         launch_chain_deep<G, LC, true>(S, A, st, lds);
     else
@@ -909,7 +909,7 @@ void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t st, Kerne
         }
         return;
     }
-#ifndef RR_LISTED  // the listed-pixel kernels serve the production dispatches only: no unfused level kernels
+#if !defined(RR_LISTED) && !defined(RR_VIEWS)  // the listed-pixel and view-batch kernels serve the production dispatches only: no unfused level kernels
     {
         Span s(prof, K_TRACE, st);
         if (A.level > 0)

@@ -1,0 +1,58 @@
+// render_views.hip — the launches of a batch of views (rr_render_views): one pass's level-0 events
+// through the scene's own in-wave kernel family, compiled with the camera-table source in namespace rr::views
+// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip).  Only the (G, LC) dispatch lives here.
+#include "kernels.hpp"
+
+namespace rr {
+
+// the pass's level-0 launch, by the scene's kernel family as launch_level / launch_chain / launch_tree
+#define RR_VIEWS_DISPATCH(CALL)                         \
+    const int g = S.general ? 2 : S.has_groups ? 1 : 0; \
+    if (g == 2) {                                       \
+        if (S.lds_culls)                                \
+            views::CALL(2, true);                       \
+        else                                            \
+            views::CALL(2, false);                      \
+    } else if (g == 1) {                                \
+        if (S.lds_culls)                                \
+            views::CALL(1, true);                       \
+        else                                            \
+            views::CALL(1, false);                      \
+    } else {                                            \
+        if (S.lds_culls)                                \
+            views::CALL(0, true);                       \
+        else                                            \
+            views::CALL(0, false);                      \
+    }                                                   \
+    return hipGetLastError()
+
+// what every rr::views kernel relies on: a camera table, whole waves per view, level 0, camera rays, none of the
+// single frame's per-camera tables (cached bundles, cost order, pixel waves, the resident loop's queue)
+static bool views_args_ok(const LevelArgs& A) {
+    return A.views && A.view_e >= 64 && A.view_e % 64 == 0 && A.level == 0 && !A.rays0 && !A.list && !A.n_dev &&
+           !A.tile_bundles && !A.tile_perm && !A.tile_cost && !A.pw && !A.deep_from && A.n % A.view_e == 0 &&
+           (int64_t)A.view_e >= A.hs * A.lrows;
+}
+
+hipError_t launch_level_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
+    if (A.n <= 0) return hipSuccess;
+    if (!views_args_ok(A) || !fused_levels(S)) return hipErrorInvalidValue;
+#define RR_CALL_LEVEL(G, LC) launch_level_t<G, LC>(S, A, st, prof)
+    RR_VIEWS_DISPATCH(RR_CALL_LEVEL);
+}
+
+hipError_t launch_chain_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
+    if (A.n <= 0) return hipSuccess;
+    if (!views_args_ok(A)) return hipErrorInvalidValue;
+#define RR_CALL_CHAIN(G, LC) launch_chain_t<G, LC>(S, A, st, prof, false)
+    RR_VIEWS_DISPATCH(RR_CALL_CHAIN);
+}
+
+hipError_t launch_tree_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
+    if (A.n <= 0) return hipSuccess;
+    if (!views_args_ok(A)) return hipErrorInvalidValue;
+#define RR_CALL_TREE(G, LC) launch_tree_t<G, LC>(S, A, st, prof)
+    RR_VIEWS_DISPATCH(RR_CALL_TREE);
+}
+
+}  // namespace rr

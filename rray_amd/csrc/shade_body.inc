@@ -15,7 +15,13 @@
 #else
     constexpr bool UH = G == 0 && !LC && FUSED && PRE && !CP && !RM && !AR;
 #endif
+#ifdef RR_VIEWS  // a view's events past its samples (sizes that are no multiple of 8) hold none
+    bool in_view = true;
+    const Px0 q0 = A.level > 0 ? Px0{0u, 0u, 0u, 0u} : level0_px<true, ORD>(A, i, -1, &in_view, tile);
+    valid = valid && in_view;
+#else
     const Px0 q0 = level0_px_if<true, ORD>(A, i, tile);
+#endif
     const uint32_t ls0 = q0.ls;
     HitRec hr;
     hr.node = -1;

@@ -475,6 +475,33 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_avg, d_mask, d_n_refined, stream)]
         check(lib().rr_render_adaptive_device(self.h, C.byref(cam), C.byref(opts), float(threshold), *p))
 
+    @staticmethod
+    def _camera_array(cams):
+        cams = list(cams)
+        return (_lib.Camera * max(len(cams), 1))(*cams), len(cams)
+
+    def render_views(self, cams, aa=1, max_depth=5, seed=0, jitter_mode=0, canvas=False):
+        """rr_render_views: a batch of cameras of one size in one call -> dict(avg=(N, H, W, 3) f64,
+        canvas=(N, vsize, hsize, 3) f64 or None, stats).  View k is render(cams[k], ...) bit for bit."""
+        arr, n = self._camera_array(cams)
+        o = _lib.RenderOpts(aa, max_depth, seed, jitter_mode, 0, 1, 8,
+                            _lib.RR_OUT_AVG | (_lib.RR_OUT_CANVAS if canvas else 0), 0, 0)
+        hs, vs = (arr[0].hsize, arr[0].vsize) if n else (0, 0)
+        out_avg = np.zeros((n, vs // max(aa, 1), hs // max(aa, 1), 3), np.float64)
+        out_canvas = np.zeros((n, vs, hs, 3), np.float64) if canvas else None
+        st = _lib.Stats()
+        check(lib().rr_render_views(self.h, arr, n, C.byref(o), _dp(out_canvas) if canvas else None, _dp(out_avg),
+                                    C.byref(st)))
+        return {"avg": out_avg, "canvas": out_canvas, "stats": st.as_dict()}
+
+    def render_views_device(self, cams, opts, d_canvas, d_avg, stream=None):
+        """rr_render_views_device: the batch into device buffers (ints: device pointers; d_avg N*H*W*3 f64 with
+        RR_OUT_AVG in opts.flags, d_canvas N*vsize*hsize*3 f64 with RR_OUT_CANVAS), ordered on `stream` (int or None),
+        not synchronised."""
+        arr, n = self._camera_array(cams)
+        p = [C.c_void_p(x) if x else None for x in (d_canvas, d_avg, stream)]
+        check(lib().rr_render_views_device(self.h, arr, n, C.byref(opts), *p))
+
     def is_shadowed(self, points, light_positions):
         p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         lp = np.ascontiguousarray(light_positions, np.float64).reshape(-1, 3)
