@@ -377,6 +377,39 @@ int rr_render_views(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const r
 int rr_render_views_device(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const rr_render_opts* opts,
                            void* d_canvas, void* d_avg, void* hip_stream);
 
+/* ---- first-hit planes of batches of views (additive to ABI 11; test RR_HAS_VIEWS_AOV) ----
+ * The guide planes that go with a batch of views: depth, normal, object id and albedo of n_views cameras of the
+ * uploaded scene in one call.  `cams` and its rules are rr_render_views' (a host array of cameras that share hsize and
+ * vsize, read before the call returns); `planes` and the plane buffers are rr_render_aov's, stacked: depth n_views x
+ * vsize x hsize doubles, normal and albedo n_views x vsize x hsize x 3 doubles, object n_views x vsize x hsize int32.
+ * View k is slice k of each plane, so a caller can wrap a plane as one tensor.  Each requested plane needs its buffer
+ * (NULL: RR_E_ARG), an unrequested plane's pointer is ignored.
+ * Definition: slice k of each requested plane is what rr_render_aov(ctx, &cams[k], opts, planes, ...) writes, bit for
+ * bit.  Planes are per canvas sample and never averaged; opts->aa only has to be consistent with the camera sizes;
+ * max_depth, seed, jitter_mode and flags are ignored.
+ * The batch runs in passes of whole views (as many as fit one pass of the context, 2^27 samples unless RRAY_BATCH says
+ * otherwise), each pass one launch of the first-hit kernel; a view's samples take whole 64-lane waves.  The
+ * RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN switches do not concern the first-hit kernel and are not refused.
+ * The call leaves the context's single-frame state (cached camera bundles, tile order, rr_resident_launch) and the
+ * colour batches alone: an rr_render, rr_render_aov or rr_render_views before and after it returns the same outputs
+ * and the same counters.
+ * rr_last_stats / stats afterwards: rays == samples == n_views * hsize * vsize, shadow_rays == shade_events ==
+ * n1n2_scans == 0, nan_rays is the sum of the single frames' values; prim_tests, exact_flops and wave_visits are
+ * reproducible but may differ from those sums (the culling bundles differ); kernel_ms is one event pair around the batch.
+ * n_views == 0: RR_OK, nothing written.  RR_E_ARG: a null ctx / cams / opts, n_views < 0, `planes` empty or with
+ * unknown bits, a requested plane with a null buffer, cameras of differing sizes, sizes inconsistent with aa,
+ * part != 0, nparts != 1, a row band, a multi-device or virtual context, no scene uploaded.  RR_E_LIMIT: one view holds
+ * more samples than one pass (render it with rr_render_aov).
+ * rr_render_views_aov: host buffers, blocking, RR_E_NAN after writing the planes when nan_rays > 0.
+ * rr_render_views_aov_device: device buffers on the context's device, everything enqueued on `hip_stream` (NULL: ctx
+ * stream) and NOT synchronised; NaN rays are reported through rr_last_stats' nan_rays. */
+#define RR_HAS_VIEWS_AOV 1
+int rr_render_views_aov(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const rr_render_opts* opts, int32_t planes,
+                        double* depth, double* normal, int32_t* object, double* albedo, rr_stats* stats);
+int rr_render_views_aov_device(rr_ctx* ctx, const rr_camera* cams, int32_t n_views, const rr_render_opts* opts,
+                               int32_t planes, void* d_depth, void* d_normal, void* d_object, void* d_albedo,
+                               void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

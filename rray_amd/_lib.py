@@ -80,7 +80,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_rccl_unique_id", "rr_create_rank", "rr_context_info", "rr_render_gather_device", "rr_create_virtual",
            "rr_unshuffle_host", "rr_stage_row_offset", "rr_build_digest", "rr_balance_bands", "rr_group_bands",
            "rr_group_set_bands", "rr_hit_at", "rr_render_aov", "rr_render_aov_device", "rr_render_adaptive",
-           "rr_render_adaptive_device", "rr_resident_launch", "rr_render_views", "rr_render_views_device"]
+           "rr_render_adaptive_device", "rr_resident_launch", "rr_render_views", "rr_render_views_device",
+           "rr_render_views_aov", "rr_render_views_aov_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -177,6 +178,10 @@ def lib():
                                   C.POINTER(Stats)]
     L.rr_render_views_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderOpts), C.c_void_p,
                                          C.c_void_p, C.c_void_p]
+    L.rr_render_views_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderOpts), C.c_int32, _D, _D,
+                                      _I, _D, C.POINTER(Stats)]
+    L.rr_render_views_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderOpts), C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

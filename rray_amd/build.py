@@ -55,7 +55,14 @@ for _u in VIEWS_UNITS:
     _like = _u.replace("render_views_", "render_")
     if _like in UNIT_FLAGS:
         UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+# first-hit planes of a batch of views (rr_render_views_aov): the first-hit kernels' camera variants with the same
+# camera-table source, each built like the render_hit_g* unit it mirrors
+VIEWS_HIT_UNITS = [f"render_views_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
+for _u in VIEWS_HIT_UNITS:
+    _like = _u.replace("render_views_hit_", "render_hit_")
+    if _like in UNIT_FLAGS:
+        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
+SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 

@@ -1778,6 +1778,144 @@ int rr_render_views(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_
     return nan ? nan_fail(nan) : RR_OK;
 }
 
+// ---- first-hit planes of batches of views (render_views.hip launch_hit_views) ----
+// what both entry points refuse before they look at the context (so a host without a device can test it)
+static int views_aov_check_args(const rr_camera* cams, int32_t n_views, const rr_render_opts* o, int32_t planes,
+                                const void* depth, const void* normal, const void* object, const void* albedo) {
+    if (!cams) return fail(RR_E_ARG, "rr_render_views_aov: null camera array");
+    if (!o) return fail(RR_E_ARG, "rr_render_views_aov: null options");
+    if (n_views < 0) return fail(RR_E_ARG, "rr_render_views_aov: n_views is negative");
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "batches of AOV frames are whole frames: part 0 of 1, no band");
+    const int32_t all = RR_AOV_DEPTH | RR_AOV_NORMAL | RR_AOV_OBJECT | RR_AOV_ALBEDO;
+    if (planes == 0 || (planes & ~all)) return fail(RR_E_ARG, "planes must be a non-empty combination of RR_AOV_*");
+    if (((planes & RR_AOV_DEPTH) && !depth) || ((planes & RR_AOV_NORMAL) && !normal) ||
+        ((planes & RR_AOV_OBJECT) && !object) || ((planes & RR_AOV_ALBEDO) && !albedo))
+        return fail(RR_E_ARG, "a requested plane has a null buffer");
+    for (int32_t k = 1; k < n_views; ++k)
+        if (cams[k].hsize != cams[0].hsize || cams[k].vsize != cams[0].vsize)
+            return fail(RR_E_ARG, "the cameras of a batch must share hsize and vsize: camera " + std::to_string(k) + " is " +
+                                      std::to_string(cams[k].hsize) + "x" + std::to_string(cams[k].vsize) + ", camera 0 " +
+                                      std::to_string(cams[0].hsize) + "x" + std::to_string(cams[0].vsize));
+    return RR_OK;
+}
+// ... and what they ask of the context and of the sizes, with the batch's pass split (nothing is enqueued before it)
+static int views_aov_validate(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_render_opts* o,
+                              rr::ViewAovPlan* plan) {
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    rr_render_opts opts = *o;
+    opts.max_depth = 0;  // ignored here (as seed, jitter_mode and flags): no recursion in a first-hit frame
+    int rc = check_opts(&cams[0], &opts);
+    if (rc != RR_OK) return rc;
+    *plan = rr::plan_views_aov(c->batch, cams[0].hsize, cams[0].vsize, n_views);
+    return plan->err != RR_OK ? fail(plan->err, plan->msg) : RR_OK;
+}
+
+int rr_render_views_aov_device(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_render_opts* o, int32_t planes,
+                               void* d_depth, void* d_normal, void* d_object, void* d_albedo, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = views_aov_check_args(cams, n_views, o, planes, d_depth, d_normal, d_object, d_albedo);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "batches of views need a single-device context (no multi-device or virtual context)");
+    if (n_views == 0) return RR_OK;
+    rr::ViewAovPlan plan{};
+    rc = views_aov_validate(c, cams, n_views, o, &plan);
+    if (rc != RR_OK) return rc;
+    const int64_t hs = cams[0].hsize, vs = cams[0].vsize, vsamples = hs * vs;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->views.ensure(((size_t)n_views + rr::RR_VIEW_TABLE_PAD) * sizeof(rr::DevView)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    // the camera table: the context's host copy (the caller's array is free after this call), then its device buffer,
+    // on the call's stream; the padding's flags say "not affine" to the last block's waves past the events
+    c->views_host.assign((size_t)n_views + rr::RR_VIEW_TABLE_PAD, rr::DevView{});
+    for (int32_t k = 0; k < n_views; ++k) {
+        rr::LevelArgs T{};
+        set_camera(T, &cams[k]);
+        c->views_host[k].cam = T.cam;
+        c->views_host[k].affine = T.cam_affine;
+    }
+    HIPCHK(hipMemcpyAsync(c->views.p, c->views_host.data(), c->views_host.size() * sizeof(rr::DevView),
+                          hipMemcpyHostToDevice, st));
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    // the single frames' per-camera state stays as it is: no cached bundles (tiles_valid), no order, no resident launch
+    rr::LevelArgs A{};
+    set_camera(A, &cams[0]);  // A.cam itself is not read: every wave takes its view's camera from the table
+    A.hs = hs;
+    A.lrows = vs;
+    A.aa = o->aa;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = o->block_rows > 0 ? o->block_rows : 8;
+    A.rays0 = nullptr;
+    A.nseg = A.nseg_out = 1;
+    A.base = 0;
+    A.level = 0;
+    A.view_e = (uint32_t)plan.view_e;  // <= the pass cap < 2^31 (plan_views_aov)
+    set_level0_index(A);
+    A.counters = frame_counters(c, 2);
+    for (int64_t v0 = 0; v0 < n_views; v0 += plan.views_per_pass) {  // a pass: whole views, one launch
+        const int64_t nv = std::min<int64_t>(plan.views_per_pass, n_views - v0);
+        A.views = c->views.as<rr::DevView>() + v0;
+        A.n = nv * plan.view_e;
+        rr::HitOut O{};
+        O.node_object = c->node_object.as<int32_t>();
+        O.depth = (planes & RR_AOV_DEPTH) ? static_cast<double*>(d_depth) + v0 * vsamples : nullptr;
+        O.normal = (planes & RR_AOV_NORMAL) ? static_cast<double*>(d_normal) + 3 * v0 * vsamples : nullptr;
+        O.object = (planes & RR_AOV_OBJECT) ? static_cast<int32_t*>(d_object) + v0 * vsamples : nullptr;
+        O.albedo = (planes & RR_AOV_ALBEDO) ? static_cast<double*>(d_albedo) + 3 * v0 * vsamples : nullptr;
+        HIPCHK(rr::launch_hit_views(c->S, A, O, st));
+    }
+    c->stats_src = frame_counters(c, 2);
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    c->stats_pending = true;
+    c->last.samples = (uint64_t)n_views * (uint64_t)vsamples;
+    c->adapt_pending = false;
+    return RR_OK;
+}
+
+int rr_render_views_aov(rr_ctx* c, const rr_camera* cams, int32_t n_views, const rr_render_opts* o, int32_t planes,
+                        double* depth, double* normal, int32_t* object, double* albedo, rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = views_aov_check_args(cams, n_views, o, planes, depth, normal, object, albedo);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "batches of views need a single-device context (no multi-device or virtual context)");
+    if (n_views == 0) return RR_OK;
+    rr::ViewAovPlan plan{};
+    rc = views_aov_validate(c, cams, n_views, o, &plan);  // before the staging buffers grow
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    // the device planes back to back, each stacked over the views: depth, normal, albedo (doubles), then object
+    const size_t total = (size_t)n_views * (size_t)cams[0].hsize * (size_t)cams[0].vsize;
+    const size_t off_normal = total * sizeof(double), off_albedo = off_normal + total * 3 * sizeof(double);
+    const size_t off_object = off_albedo + total * 3 * sizeof(double);
+    HIPCHK(c->aov.ensure(off_object + total * sizeof(int32_t)));
+    char* base = c->aov.as<char>();
+    rc = rr_render_views_aov_device(c, cams, n_views, o, planes, base, base + off_normal, base + off_object,
+                                    base + off_albedo, nullptr);
+    if (rc != RR_OK) return rc;
+    hipStream_t st = c->stream;
+    if (planes & RR_AOV_DEPTH) HIPCHK(hipMemcpyAsync(depth, base, total * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_NORMAL)
+        HIPCHK(hipMemcpyAsync(normal, base + off_normal, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_ALBEDO)
+        HIPCHK(hipMemcpyAsync(albedo, base + off_albedo, total * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (planes & RR_AOV_OBJECT)
+        HIPCHK(hipMemcpyAsync(object, base + off_object, total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
+}
+
 }  // extern "C"
 
 // ---- ABI 10: cost-balanced bands (multi.cpp) ----

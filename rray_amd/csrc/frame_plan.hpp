@@ -137,6 +137,45 @@ struct FrameRequest {
 
 // level-0 events of one view of a batch: its samples rounded up to whole waves, so a wave never holds two views
 inline int64_t view_events(int64_t hs, int64_t lrows) { return (hs * lrows + 63) / 64 * 64; }
+// level-0 events one pass of a batch of views may hold: the context's batch, indexed in 32 bits as a part's samples
+inline int64_t view_pass_cap(int64_t batch) { return std::min<int64_t>(batch, ((int64_t)1 << 31) - 64); }
+// whole views per pass of a batch of `views` views of view_e events each (never more than the batch has), or 0 when
+// one view does not fit a pass
+inline int64_t views_in_pass(int64_t batch, int64_t view_e, int64_t views) {
+    const int64_t cap = view_pass_cap(batch);
+    return view_e > cap ? 0 : std::min<int64_t>(cap / view_e, views);
+}
+
+// The pass split of rr_render_views_aov (first-hit planes of a batch of views): the view branch of
+// plan_frame's arithmetic and nothing else of a frame's plan — the first-hit kernel has no family, no queues, no
+// order and no resident loop.  Pass p renders views [p * views_per_pass, min(views, (p + 1) * views_per_pass)).
+struct ViewAovPlan {
+    int64_t view_e;          // level-0 events of one view (view_events)
+    int64_t views_per_pass;  // whole views per launch
+    int64_t passes;          // launches
+    bool tile_fast;          // every view is full 8x8 tiles
+    int err;                 // RR_OK, or RR_E_ARG / RR_E_LIMIT and its text
+    const char* msg;
+};
+inline ViewAovPlan plan_views_aov(int64_t batch, int64_t hs, int64_t lrows, int32_t views) {
+    ViewAovPlan p{};
+    if (hs <= 0 || lrows <= 0 || views < 0 || batch <= 0 || hs > ((int64_t)1 << 31) || lrows > ((int64_t)1 << 31)) {
+        p.err = RR_E_ARG;
+        p.msg = "internal: a view batch is views of hs x lrows samples, hs and lrows in 1 .. 2^31";
+        return p;
+    }
+    p.view_e = view_events(hs, lrows);
+    p.tile_fast = full_tiles(false, hs, lrows, 0);
+    if (views == 0) return p;
+    p.views_per_pass = views_in_pass(batch, p.view_e, views);
+    if (p.views_per_pass == 0) {
+        p.err = RR_E_LIMIT;
+        p.msg = "one view's samples must fit one pass of the context (render such a view with rr_render_aov)";
+        return p;
+    }
+    p.passes = (views + p.views_per_pass - 1) / p.views_per_pass;
+    return p;
+}
 
 struct FramePlan {
     Family family;
@@ -218,13 +257,12 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
             return f;
         }
         // a pass's samples are indexed in 32 bits, as a part's
-        const int64_t pass_cap = std::min<int64_t>(r.batch, ((int64_t)1 << 31) - 64);
-        if (r.view_e > pass_cap) {
+        f.views_per_pass = views_in_pass(r.batch, r.view_e, r.views);
+        if (f.views_per_pass == 0) {
             f.err = RR_E_LIMIT;
             f.msg = "one view's samples must fit one pass of the context (render such a view with rr_render)";
             return f;
         }
-        f.views_per_pass = std::min<int64_t>(pass_cap / r.view_e, r.views);
         f.B = f.views_per_pass * r.view_e;
         f.passes = false;
     }

@@ -310,5 +310,13 @@ constexpr int RR_HIT_DOUBLES = 23;
 template <int G, bool LC>
 void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
 hipError_t launch_hit(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+// First-hit planes of a batch of views (rr_render_views_aov): hit_kernel's camera variants compiled
+// once more in namespace rr::views (render_views_hit_g<G>_<lds|gl>.hip).  One pass of whole views per launch: A.views
+// and O's planes start at the pass's first view, A.n = the pass's views * A.view_e, A.base 0, no cached bundles.
+namespace views {
+template <int G, bool LC>
+void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+}  // namespace views
+hipError_t launch_hit_views(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
 
 }  // namespace rr

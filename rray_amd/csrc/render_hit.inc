@@ -19,6 +19,12 @@
 // device functions (tests/test_gpu_fuzz.py holds their frames to the oracle bit for bit), and the culls only skip
 // nodes whose exact test cannot report an entry (DESIGN.md §3.5).  The walks do not read across lanes (XL off, as
 // the tree kernels), so a VGPR spill could only cost time, never a result.
+// RR_VIEWS (namespace rr::views, render_views_hit_g<G>_<lds|gl>.hip: rr_render_views_aov): the CAM kernels once more
+// with the camera-table source.  A pass is whole views of whole waves; a lane is valid when it is inside the launch
+// and holds a sample of its view (level0_px's ok), q.ls is its slot in the pass's stacked planes, and there is no
+// cached bundle (A.tile_bundles == null): full tiles of an affine view build the corner bundle in the walk (cam_tile
+// from the table), every other wave its bundle from its own rays.  Waves of the last block past the events read the
+// table's padding (RR_VIEW_TABLE_PAD) for their flag.
 // CP: material_color may meet a tree-evaluated pattern (gradient / blend / perturbed / noise / texture: the scene's
 // complex_patterns); only the albedo plane reads it.
 //
@@ -41,9 +47,18 @@ __global__ void __launch_bounds__(256) RR_HIT_ATTR(G, CAM, CP) hit_kernel(DevSce
     const uint32_t wave64 = (uint32_t)uniform((int)(threadIdx.x & ~63u));
     const int wave = (int)(wave64 >> 6);
     const int64_t i = (int64_t)(blockIdx.x * RR_BLOCK + wave64 + (uint32_t)lane_id());
+#ifdef RR_VIEWS
+    // a batch of views (rr_render_views_aov): every view takes whole waves, so a ragged view's last wave has idle
+    // lanes inside the launch, not only at its end (level0_px's ok); q.ls is the slot in the pass's stacked planes
+    bool in_px = true;
+    const Px0 q = level0_px<true>(A, i, wave, &in_px);
+    const bool valid = i < n_live && in_px;
+    Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#else
     const bool valid = i < n_live;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const Px0 q = level0_px<true>(A, i, wave);
+#endif
     Ray r = {mk(0, 0, 0), mk(0, 0, 1)};
     if (valid) {
         uint64_t s0 = 0;
@@ -106,9 +121,13 @@ template <int G, bool LC>
 void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
     const dim3 grid(blocks_for(A.n)), block(256);
     const size_t lds = cull_lds(S);
+#ifdef RR_VIEWS  // camera samples only (launch_hit_views refuses a ray batch): the CAM instantiations
+    if (O.albedo && S.complex_patterns) {
+#else
     if (A.rays0) {
         hipLaunchKernelGGL((hit_kernel<G, LC, false, true>), grid, block, lds, st, S, A, O);
     } else if (O.albedo && S.complex_patterns) {
+#endif
         hipLaunchKernelGGL((hit_kernel<G, LC, true, false, true>), grid, block, lds, st, S, A, O);
     } else {
         hipLaunchKernelGGL((hit_kernel<G, LC, true, false, false>), grid, block, lds, st, S, A, O);

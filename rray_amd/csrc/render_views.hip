@@ -1,6 +1,7 @@
 // render_views.hip — the launches of a batch of views (rr_render_views): one pass's level-0 events
 // through the scene's own in-wave kernel family, compiled with the camera-table source in namespace rr::views
-// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip).  Only the (G, LC) dispatch lives here.
+// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip), and a pass of rr_render_views_aov (§3.17) through the first-hit
+// kernel compiled the same way (render_views_hit_g<G>_<lds|gl>.hip).  Only the (G, LC) dispatch lives here.
 #include "kernels.hpp"
 
 namespace rr {
@@ -53,6 +54,17 @@ hipError_t launch_tree_views(const DevScene& S, const LevelArgs& A, hipStream_t 
     if (!views_args_ok(A)) return hipErrorInvalidValue;
 #define RR_CALL_TREE(G, LC) launch_tree_t<G, LC>(S, A, st, prof)
     RR_VIEWS_DISPATCH(RR_CALL_TREE);
+}
+
+// one pass of rr_render_views_aov: the first-hit kernel over the pass's views (render_views_hit_g<G>_<lds|gl>.hip).
+// It counts into the query buffer and clears nothing (no counters_zero); the planes it writes are the ones O names
+hipError_t launch_hit_views(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
+    if (A.n <= 0) return hipSuccess;
+    if (!views_args_ok(A) || A.base != 0 || A.n >= ((int64_t)1 << 31) || A.counters_zero || !O.node_object ||
+        !(O.depth || O.normal || O.object || O.albedo))
+        return hipErrorInvalidValue;
+#define RR_CALL_HIT(G, LC) launch_hit_t<G, LC>(S, A, O, st)
+    RR_VIEWS_DISPATCH(RR_CALL_HIT);
 }
 
 }  // namespace rr

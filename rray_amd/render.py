@@ -502,6 +502,39 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_canvas, d_avg, stream)]
         check(lib().rr_render_views_device(self.h, arr, n, C.byref(opts), *p))
 
+    def render_views_aov(self, cams, aa=1, planes=("depth", "normal", "object", "albedo")):
+        """rr_render_views_aov: the first-hit planes of a batch of cameras of one size in one call -> dict of depth
+        (N, vsize, hsize) f64 (+inf: miss), normal (N, vsize, hsize, 3), object (N, vsize, hsize) int32 (-1: miss),
+        albedo (N, vsize, hsize, 3), and stats.  Slice k of each plane is render_aov(cams[k], aa, planes)'s, bit for
+        bit; never averaged: aa only has to divide the camera sizes."""
+        mask = self._aov_mask(planes)
+        arr, n = self._camera_array(cams)
+        o = _lib.RenderOpts(aa, 0, 0, 0, 0, 1, 8, 0, 0, 0)
+        hs, vs = (arr[0].hsize, arr[0].vsize) if n else (0, 0)
+        out = {"depth": np.zeros((n, vs, hs), np.float64) if "depth" in planes else None,
+               "normal": np.zeros((n, vs, hs, 3), np.float64) if "normal" in planes else None,
+               "object": np.zeros((n, vs, hs), np.int32) if "object" in planes else None,
+               "albedo": np.zeros((n, vs, hs, 3), np.float64) if "albedo" in planes else None}
+        st = _lib.Stats()
+        check(lib().rr_render_views_aov(self.h, arr, n, C.byref(o), mask,
+                                        _dp(out["depth"]) if out["depth"] is not None else None,
+                                        _dp(out["normal"]) if out["normal"] is not None else None,
+                                        _ip(out["object"]) if out["object"] is not None else None,
+                                        _dp(out["albedo"]) if out["albedo"] is not None else None, C.byref(st)))
+        res = {k: v for k, v in out.items() if v is not None}
+        res["stats"] = st.as_dict()
+        return res
+
+    def render_views_aov_device(self, cams, opts, planes, d_depth=None, d_normal=None, d_object=None, d_albedo=None,
+                                stream=None):
+        """rr_render_views_aov_device: the stacked planes into device buffers (ints: device pointers; depth N*vsize*hsize
+        f64, normal and albedo N*vsize*hsize*3 f64, object N*vsize*hsize int32), ordered on `stream` (int or None), not
+        synchronised.  planes: names or an RR_AOV_* mask."""
+        mask = planes if isinstance(planes, int) else self._aov_mask(planes)
+        arr, n = self._camera_array(cams)
+        p = [C.c_void_p(x) if x else None for x in (d_depth, d_normal, d_object, d_albedo, stream)]
+        check(lib().rr_render_views_aov_device(self.h, arr, n, C.byref(opts), mask, *p))
+
     def is_shadowed(self, points, light_positions):
         p = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         lp = np.ascontiguousarray(light_positions, np.float64).reshape(-1, 3)
