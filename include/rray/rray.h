@@ -410,6 +410,44 @@ int rr_render_views_aov_device(rr_ctx* ctx, const rr_camera* cams, int32_t n_vie
                                int32_t planes, void* d_depth, void* d_normal, void* d_object, void* d_albedo,
                                void* hip_stream);
 
+/* ---- device-resident ray queries (additive to ABI 11; test RR_HAS_RAYS_DEVICE) ----
+ * The ray queries for callers whose rays live in HBM: lenses that are not a pinhole (fisheye, panorama, thin lens,
+ * distortion), rays sampled by a network, picking rays, visibility between point pairs.  Device buffers on the context's
+ * device; the work is enqueued on `hip_stream` (NULL: ctx stream) and NOT synchronised, with the stream claim of the
+ * other _device entries.  Inputs are read in place — no copy, no pack kernel — and must stay valid until the stream
+ * reaches the end of the call's work; outputs must not overlap inputs.
+ * Ray layout: ray i is six doubles at d_rays + 6 * i, origin xyz then direction xyz (torch.cat([origins, directions],
+ * 1) of two n x 3 tensors).
+ * rr_camera_rays_device: the hsize * vsize rays of `cam`, row-major (ray py * hsize + px is Camera::ray_for_pixel(px,
+ *   py), camera.rs:75-93), computed by the device function the frames use: the colour frame's rays bit for bit.  Needs
+ *   no scene.  RR_E_ARG: a null ctx / cam / d_rays, hsize or vsize < 1.  RR_E_LIMIT: hsize * vsize >= 2^32.
+ * rr_color_at_device: d_rgb[i] (3 doubles) is what rr_color_at writes for ray i of the same batch, bit for bit.  Ray
+ *   i's area-light jitter identity is sample i, path 1, under `seed` — the identity of sample i of a camera frame, so
+ *   rr_color_at_device over rr_camera_rays_device(cam) is the canvas of rr_render(cam) with the same remaining / seed /
+ *   jitter_mode.
+ * rr_hit_at_device: d_hits holds n rr_hit records (192 bytes each, the host struct's layout: word 0 = {object, inside},
+ *   words 1..23 = t, u, v, point, eyev, normalv, over_point, under_point, reflectv, n1, n2); record i equals the one
+ *   rr_hit_at writes, every field bit for bit.  The batch runs in passes of at most min(context batch, 2^22) rays, so the
+ *   context's staging planes stay below 2^22 * 192 bytes whatever n is.
+ * rr_is_shadowed_device: d_points and d_light_positions are two n x 3 double arrays, d_out n int32; d_out[i] equals
+ *   rr_is_shadowed's value.  rr_last_stats is not touched.
+ * The three queries.  n == 0: RR_OK, nothing enqueued.  RR_E_ARG: a null ctx, a null buffer when n > 0, n < 0, no scene
+ * uploaded, a multi-device or virtual context (the buffers belong to one device).  RR_E_LIMIT: `remaining` outside
+ * 0..RR_MAX_DEPTH, n >= 2^32 (the sample index is 32-bit).  They never return RR_E_NAN: NaN rays are reported through
+ * rr_last_stats' nan_rays (the count rr_color_at / rr_hit_at would have turned into RR_E_NAN).
+ * rr_last_stats after rr_color_at_device / rr_hit_at_device: samples == n and the call's own counters (for hits: rays
+ * == n, n1n2_scans == the number of hits, shadow_rays == shade_events == 0); kernel_ms is one event pair around the
+ * call's work.
+ * The calls leave the context's frame state alone (cached camera bundles, tile order, rr_resident_launch, the frames'
+ * counter buffers): an rr_render or rr_render_views before and after them returns the same image and counters. */
+#define RR_HAS_RAYS_DEVICE 1
+int rr_camera_rays_device(rr_ctx* ctx, const rr_camera* cam, void* d_rays, void* hip_stream);
+int rr_color_at_device(rr_ctx* ctx, int64_t n, const void* d_rays, int32_t remaining, uint64_t seed,
+                       int32_t jitter_mode, void* d_rgb, void* hip_stream);
+int rr_hit_at_device(rr_ctx* ctx, int64_t n, const void* d_rays, void* d_hits, void* hip_stream);
+int rr_is_shadowed_device(rr_ctx* ctx, int64_t n, const void* d_points, const void* d_light_positions, void* d_out,
+                          void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

@@ -81,7 +81,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_unshuffle_host", "rr_stage_row_offset", "rr_build_digest", "rr_balance_bands", "rr_group_bands",
            "rr_group_set_bands", "rr_hit_at", "rr_render_aov", "rr_render_aov_device", "rr_render_adaptive",
            "rr_render_adaptive_device", "rr_resident_launch", "rr_render_views", "rr_render_views_device",
-           "rr_render_views_aov", "rr_render_views_aov_device"]
+           "rr_render_views_aov", "rr_render_views_aov_device", "rr_camera_rays_device", "rr_color_at_device",
+           "rr_hit_at_device", "rr_is_shadowed_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -182,6 +183,12 @@ def lib():
                                       _I, _D, C.POINTER(Stats)]
     L.rr_render_views_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderOpts), C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # device-resident ray queries (RR_HAS_RAYS_DEVICE): device pointers and the stream as integers
+    L.rr_camera_rays_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_void_p]
+    L.rr_color_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p,
+                                     C.c_void_p]
+    L.rr_hit_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rr_is_shadowed_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -62,7 +62,9 @@ for _u in VIEWS_HIT_UNITS:
     _like = _u.replace("render_views_hit_", "render_hit_")
     if _like in UNIT_FLAGS:
         UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip", "api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
+# device-resident ray queries (rr_camera_rays_device, rr_hit_at_device): the camera-ray and record-writer kernels
+RAYS_UNITS = ["render_rays.hip"]
+SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip"] + RAYS_UNITS + ["api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
                                          "imgfmt.cpp"]
 
 

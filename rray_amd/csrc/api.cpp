@@ -81,6 +81,9 @@ struct rr_ctx {
     // first-hit queries (hit_kernel): node index -> rr_scene_desc object id (flatten's node_of_object inverted, built
     // at upload), and rr_hit_at's result planes
     DBuf node_object, hitrec, aov;  // aov: rr_render_aov's device planes
+    // rr_is_shadowed_device's walk counters: a sink nobody reads, so that the query leaves pending stats (which may be
+    // the query buffer's) as they are
+    DBuf shadow_sink;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -901,7 +904,8 @@ void rr_destroy(rr_ctx* c) {
     for (DBuf* b : {&c->culls, &c->inner, &c->chunks, &c->nodes, &c->groups, &c->shapes, &c->tris, &c->mats, &c->pats, &c->lights, &c->textures, &c->texels, &c->counters,
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
-                    &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views})
+                    &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
+                    &c->shadow_sink})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -1914,6 +1918,143 @@ int rr_render_views_aov(rr_ctx* c, const rr_camera* cams, int32_t n_views, const
     if (rc != RR_OK) return rc;
     const uint64_t nan = (stats ? stats : &local)->nan_rays;
     return nan ? nan_fail(nan) : RR_OK;
+}
+
+// ---- device-resident ray queries (render_rays.hip) ----
+// The caller's buffers go to the kernels as they are (LevelArgs.rays0 / out, launch_shadow_query's arrays); nothing is
+// staged but rr_hit_at_device's planes, nothing is copied to the host and nothing waits.  None of them touches the
+// frames' state: no tile_bundles (tiles_valid), no order, no begin_frame_counters (persist_last), counters in buffer 2.
+int rr_camera_rays_device(rr_ctx* c, const rr_camera* cam, void* d_rays, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (!c || !cam || !d_rays) return fail(RR_E_ARG, "rr_camera_rays_device: null argument");
+    if (c->group) return fail(RR_E_ARG, "device-resident ray queries need a single-device context (no multi-device or virtual context)");
+    if (cam->hsize < 1 || cam->vsize < 1) return fail(RR_E_ARG, "camera sizes must be >= 1");
+    if (cam->hsize >= ((int64_t)1 << 32) || cam->vsize >= ((int64_t)1 << 32) ||
+        cam->hsize * cam->vsize >= ((int64_t)1 << 32))
+        return fail(RR_E_LIMIT, "a camera's rays must number fewer than 2^32");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    rr::LevelArgs A{};
+    set_camera(A, cam);  // the frames' DevCamera and affine flag
+    HIPCHK(rr::launch_camera_rays(A.cam, A.cam_affine != 0, cam->hsize * cam->vsize, static_cast<double*>(d_rays), st));
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+// what the three queries refuse alike (n == 0 is the caller's early RR_OK, after these)
+static int rays_check(const rr_ctx* c, int64_t n, bool null_buffer) {
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "device-resident ray queries need a single-device context (no multi-device or virtual context)");
+    if (n < 0) return fail(RR_E_ARG, "n is negative");
+    if (n > 0 && null_buffer) return fail(RR_E_ARG, "null device buffer");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    if (n >= ((int64_t)1 << 32)) return fail(RR_E_LIMIT, "a ray batch must hold fewer than 2^32 rays");
+    return RR_OK;
+}
+// the call's counters are the context's pending stats (rr_render_views_aov_device's pattern)
+static void rays_stats_pending(rr_ctx* c, int64_t n) {
+    c->stats_src = frame_counters(c, 2);
+    c->stats_pending = true;
+    c->last.samples = (uint64_t)n;
+    c->adapt_pending = false;
+}
+
+int rr_color_at_device(rr_ctx* c, int64_t n, const void* d_rays, int32_t remaining, uint64_t seed, int32_t jitter_mode,
+                       void* d_rgb, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = rays_check(c, n, !d_rays || !d_rgb);
+    if (rc != RR_OK) return rc;
+    if (remaining < 0 || remaining > RR_MAX_DEPTH) return fail(RR_E_LIMIT, "remaining out of range");
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    const int saved_epoch = c->epoch;
+    c->epoch = 2;  // the query buffer (frame buffers keep their state)
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));
+    rr::LevelArgs A{};  // rr_color_at's level 0 on the caller's rays: sample i's jitter identity is (i, path 1)
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.rays0 = static_cast<const double*>(d_rays);
+    A.seed = seed;
+    A.jitter_mode = jitter_mode;
+    rc = run_levels(c, frame_facts(c, remaining), A, n, remaining, static_cast<double*>(d_rgb), st);
+    c->epoch = saved_epoch;
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n);
+    return RR_OK;
+}
+
+int rr_hit_at_device(rr_ctx* c, int64_t n, const void* d_rays, void* d_hits, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = rays_check(c, n, !d_rays || !d_hits);
+    if (rc != RR_OK) return rc;
+    if (n == 0) return RR_OK;
+    const rr::RayPassPlan plan = rr::plan_ray_passes(n, c->batch);
+    HIPCHK(hipSetDevice(c->device));
+    // one pass's records as planes: RR_HIT_DOUBLES double planes, then the two int planes (never more than
+    // kRayPassMax * 192 bytes, whatever n is)
+    const size_t d_bytes = (size_t)plan.pass * rr::RR_HIT_DOUBLES * sizeof(double);
+    HIPCHK(c->hitrec.ensure(d_bytes + (size_t)plan.pass * 2 * sizeof(int32_t)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.rec_d = c->hitrec.as<double>();
+    O.rec_i = reinterpret_cast<int32_t*>(c->hitrec.as<char>() + d_bytes);
+    O.stride = plan.pass;
+    rr::LevelArgs A{};
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.nseg = A.nseg_out = 1;
+    A.counters = frame_counters(c, 2);
+    A.base = 0;
+    for (int64_t first = 0; first < n; first += plan.pass) {  // a pass: the planes of its rays, then their records
+        const int64_t np = std::min<int64_t>(plan.pass, n - first);
+        A.rays0 = static_cast<const double*>(d_rays) + 6 * first;
+        A.n = np;
+        set_level0_index(A);
+        HIPCHK(rr::launch_hit(c->S, A, O, st));
+        HIPCHK(rr::launch_hit_records(O, np, static_cast<char*>(d_hits) + sizeof(rr_hit) * (size_t)first, st));
+    }
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n);
+    return RR_OK;
+}
+
+int rr_is_shadowed_device(rr_ctx* c, int64_t n, const void* d_points, const void* d_light_positions, void* d_out,
+                          void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = rays_check(c, n, !d_points || !d_light_positions || !d_out);
+    if (rc != RR_OK) return rc;
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->shadow_sink.ensure(kCounterBytes));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    HIPCHK(rr::launch_shadow_query(c->S, static_cast<const double*>(d_points), static_cast<const double*>(d_light_positions),
+                                   n, static_cast<int32_t*>(d_out), c->shadow_sink.as<unsigned long long>(), st));
+    HIPCHK(claim.release());
+    return RR_OK;
 }
 
 }  // extern "C"

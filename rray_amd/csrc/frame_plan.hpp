@@ -177,6 +177,24 @@ inline ViewAovPlan plan_views_aov(int64_t batch, int64_t hs, int64_t lrows, int3
     return p;
 }
 
+// The pass split of rr_hit_at_device (first hits of a device-resident ray batch): the first-hit
+// kernel writes a pass's records as planes into the context's staging buffer and hit_records_kernel turns them into
+// the caller's records, so a pass holds at most min(batch, kRayPassMax) rays and the staging never exceeds
+// kRayPassMax * sizeof(rr_hit) bytes.  Pass p holds rays [p * pass, min(n, (p + 1) * pass)): every pass but the last is
+// `pass` rays, and the sizes sum to n.  n <= 0 (or batch <= 0): no pass.
+constexpr int64_t kRayPassMax = (int64_t)1 << 22;
+struct RayPassPlan {
+    int64_t pass;    // rays per pass (the last may be shorter)
+    int64_t passes;  // launches
+};
+inline RayPassPlan plan_ray_passes(int64_t n, int64_t batch) {
+    RayPassPlan p{};
+    if (n <= 0 || batch <= 0) return p;
+    p.pass = std::min<int64_t>(std::min<int64_t>(batch, kRayPassMax), n);
+    p.passes = (n + p.pass - 1) / p.pass;
+    return p;
+}
+
 struct FramePlan {
     Family family;
     bool fused, ext;  // segmented queues between the levels; refraction halves beside the pending sums

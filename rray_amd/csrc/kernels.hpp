@@ -319,4 +319,13 @@ void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStr
 }  // namespace views
 hipError_t launch_hit_views(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
 
+// Device-resident ray queries (render_rays.hip).
+// camera_rays_kernel: the n = cam.hsize * cam.vsize (< 2^32) rays of a camera, row-major, six doubles each (origin,
+// direction: LevelArgs.rays0's layout), by the frames' camera_ray on the frames' DevCamera / affine flag (api.cpp
+// set_camera).
+hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t stream);
+// hit_records_kernel: the first n entries of hit_kernel's ray-batch planes (O.rec_i / O.rec_d, O.stride entries per
+// plane) as n rr_hit records at `out`; n <= 2^24 (one pass of rr_hit_at_device holds at most 2^22).
+hipError_t launch_hit_records(const HitOut& O, int64_t n, void* out, hipStream_t stream);
+
 }  // namespace rr

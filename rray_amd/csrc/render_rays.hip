@@ -1,0 +1,101 @@
+// render_rays.hip — the two kernels of the device-resident ray queries:
+//   camera_rays_kernel  Camera::ray_for_pixel (camera.rs:75-93) of every canvas sample into a caller's ray buffer
+//                       (rr_camera_rays_device), by render_common.inc's camera_ray: the frames' own arithmetic
+//   hit_records_kernel  one pass of hit_kernel's ray-batch planes (HitOut.rec_i / rec_d) -> rr_hit records in the
+//                       caller's buffer (rr_hit_at_device)
+// Neither reads the scene.  The queries' walks are the existing kernels' (hit_kernel's ray-batch instantiation, the
+// colour families with A.rays0, shadow_query_kernel), launched on the caller's buffers as they are.
+#include <cstdlib>
+
+#include "device_core.inc"
+#include "kernels.hpp"
+#include "wavefront.hpp"
+
+namespace rr {
+#include "render_common.inc"
+
+// One lane per ray, row-major: ray i is sample (i % hsize, i / hsize) in 32-bit arithmetic (n < 2^32, host-checked).
+// The last wave may be short.  A lane's six doubles are 48 consecutive bytes and a wave's rays 3 KiB of consecutive
+// cache lines, each written whole by the wave's six stores.
+__global__ void __launch_bounds__(256) camera_rays_kernel(DevCamera C, int32_t affine, uint32_t hsize, int64_t n,
+                                                          double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * RR_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = (uint32_t)i;
+    const uint32_t py = t / hsize, px = t - py * hsize;
+    const Ray r = camera_ray(C, affine != 0, px, py);
+    double* o = out + 6 * i;
+    o[0] = r.o.x;
+    o[1] = r.o.y;
+    o[2] = r.o.z;
+    o[3] = r.d.x;
+    o[4] = r.d.y;
+    o[5] = r.d.z;
+}
+
+// rr_hit as 8-byte words: word 0 = {object (low), inside (high)}, words 1..23 = the RR_HIT_DOUBLES planes in the
+// struct's order.  A block turns RR_REC_TILE consecutive records of the pass into records: the planes are read 64
+// consecutive entries per wave (whole 512-byte runs of one plane; the int planes 256-byte runs) into an LDS tile, and
+// the tile goes out as RR_REC_TILE * 24 consecutive words, lane after lane, so every store instruction of a wave covers
+// four whole cache lines.  The tile is field-major with rows padded by one word: the plane-side writes are
+// conflict-free, the record-side reads at most two-way.  Any pass size >= 1: a short last tile reads and writes only
+// its n - first records.
+constexpr int RR_REC_WORDS = 1 + RR_HIT_DOUBLES;  // 24
+constexpr int RR_REC_TILE = 64;
+constexpr int RR_REC_ROW = RR_REC_TILE + 1;
+static_assert(RR_REC_WORDS * 8 == 192, "rr_hit is 24 words of 8 bytes (rray.h)");
+static_assert(RR_REC_WORDS % 4 == 0 && (RR_REC_TILE * RR_REC_WORDS) % (int)RR_BLOCK == 0, "whole block iterations");
+
+__global__ void __launch_bounds__(256) hit_records_kernel(const int32_t* __restrict__ rec_i,
+                                                          const double* __restrict__ rec_d, int64_t stride, int64_t n,
+                                                          unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long tile[RR_REC_WORDS * RR_REC_ROW];
+    const int64_t first = (int64_t)blockIdx.x * RR_REC_TILE;
+    const int64_t left = n - first;
+    const int m = left < RR_REC_TILE ? (int)left : RR_REC_TILE;  // records of this tile (>= 1: the grid is ceil)
+    const int r = (int)(threadIdx.x & 63u), w4 = (int)(threadIdx.x >> 6);
+#pragma unroll
+    for (int it = 0; it < RR_REC_WORDS / 4; ++it) {  // four planes per step, one per wave
+        const int f = it * 4 + w4;
+        unsigned long long v = 0ull;
+        if (r < m) {
+            const int64_t j = first + r;
+            if (f == 0) {
+                const uint32_t object = (uint32_t)rec_i[j], inside = (uint32_t)rec_i[stride + j];
+                v = (unsigned long long)object | ((unsigned long long)inside << 32);
+            } else {
+                v = (unsigned long long)__double_as_longlong(rec_d[(int64_t)(f - 1) * stride + j]);
+            }
+        }
+        tile[f * RR_REC_ROW + r] = v;
+    }
+    __syncthreads();
+    unsigned long long* o = out + first * RR_REC_WORDS;
+    const int words = m * RR_REC_WORDS;
+#pragma unroll
+    for (int it = 0; it < RR_REC_TILE * RR_REC_WORDS / (int)RR_BLOCK; ++it) {
+        const int w = it * (int)RR_BLOCK + (int)threadIdx.x;
+        const int rec = w / RR_REC_WORDS, f = w - rec * RR_REC_WORDS;
+        if (w < words) o[w] = tile[f * RR_REC_ROW + rec];
+    }
+}
+
+hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!out || cam.hsize < 1 || cam.vsize < 1 || n != cam.hsize * cam.vsize || n >= ((int64_t)1 << 32))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks_for(n)), dim3(RR_BLOCK), 0, st, cam, affine ? 1 : 0,
+                       (uint32_t)cam.hsize, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_hit_records(const HitOut& O, int64_t n, void* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!O.rec_i || !O.rec_d || !out || O.stride < n || n > ((int64_t)1 << 24)) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((n + RR_REC_TILE - 1) / RR_REC_TILE);
+    hipLaunchKernelGGL(hit_records_kernel, dim3(grid), dim3(RR_BLOCK), 0, st, O.rec_i, O.rec_d, O.stride, n,
+                       static_cast<unsigned long long*>(out));
+    return hipGetLastError();
+}
+
+}  // namespace rr

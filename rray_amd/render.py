@@ -542,6 +542,42 @@ class Renderer:
         check(lib().rr_is_shadowed(self.h, len(p), _dp(p), _dp(lp), _ip(out)))
         return out.astype(bool)
 
+    # ---- device-resident ray queries (rray.h RR_HAS_RAYS_DEVICE): device pointers as ints, nothing synchronised ----
+    def camera_rays_device(self, cam, d_rays, stream=None):
+        """rr_camera_rays_device: the hsize * vsize rays of `cam` into d_rays (int: a device pointer to hsize * vsize * 6
+        f64), row-major, ray py * hsize + px = origin xyz, direction xyz — the colour frame's rays bit for bit.  Ordered
+        on `stream` (int or None), not synchronised; no scene needed.  With torch:
+            rays = torch.empty((cam.vsize * cam.hsize, 6), dtype=torch.float64, device=dev)
+            r.camera_rays_device(cam, rays.data_ptr(), torch.cuda.current_stream().cuda_stream)"""
+        p = [C.c_void_p(x) if x else None for x in (d_rays, stream)]
+        check(lib().rr_camera_rays_device(self.h, C.byref(cam), *p))
+
+    def color_at_device(self, n, d_rays, d_rgb, remaining=5, seed=0, jitter_mode=0, stream=None):
+        """rr_color_at_device: Scene::color_at of n rays read in place from d_rays (n x 6 f64: origin, direction;
+        torch.cat([origins, directions], 1) for a caller who holds the two apart) into d_rgb (n x 3 f64), what
+        color_at returns for the same rays bit for bit.  Ray i's area-light jitter identity is sample i, so the rays
+        of camera_rays_device(cam) give render(cam, canvas=True)'s canvas.  NaN rays are counted in
+        last_stats()['nan_rays'], never raised."""
+        p = [C.c_void_p(x) if x else None for x in (d_rays,)]
+        q = [C.c_void_p(x) if x else None for x in (d_rgb, stream)]
+        check(lib().rr_color_at_device(self.h, n, *p, remaining, seed, jitter_mode, *q))
+
+    def hit_at_device(self, n, d_rays, d_hits, stream=None):
+        """rr_hit_at_device: n rr_hit records (192 bytes each, _lib.hit_dtype()'s layout) into d_hits, record i what
+        hit_at returns for ray i bit for bit.  With torch:
+            hits = torch.empty((n, 192), dtype=torch.uint8, device=dev)
+            r.hit_at_device(n, rays.data_ptr(), hits.data_ptr(), stream)
+            hits.view(torch.float64)      # (n, 24): column 1 t, 4:7 point, 10:13 normalv, 22:24 n1, n2
+            hits.view(torch.int32)[:, :2]  # object, inside (a miss: object -1, everything else 0)"""
+        p = [C.c_void_p(x) if x else None for x in (d_rays, d_hits, stream)]
+        check(lib().rr_hit_at_device(self.h, n, *p))
+
+    def is_shadowed_device(self, n, d_points, d_light_positions, d_out, stream=None):
+        """rr_is_shadowed_device: Scene::is_shadowed of n (point, light position) pairs — two n x 3 f64 device arrays —
+        into d_out (n int32: 0 / 1), is_shadowed's values.  last_stats() is left as it is."""
+        p = [C.c_void_p(x) if x else None for x in (d_points, d_light_positions, d_out, stream)]
+        check(lib().rr_is_shadowed_device(self.h, n, *p))
+
 
 def adaptive_mask(frame, threshold):
     """The adaptive frames' criterion in numpy (rray.h rr_render_adaptive, rule 2): pixel p of frame (H, W, 3) is
