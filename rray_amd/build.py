@@ -25,47 +25,62 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",
           "-I" + os.path.join(ROOT, "include")]
 DEVICE = ["--offload-arch=" + ARCH, "-mllvm", "-disable-promote-alloca-to-lds"]
-LEVEL_UNITS = [f"render_levels_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]  # slowest first
-CHAIN_UNITS = [f"render_chain_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
-TREE_UNITS = [f"render_tree_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
-# per-unit flags: the chain kernels' loop must not get loop-invariant constants hoisted into registers (they
-# spill instead of being rematerialised)
-UNIT_FLAGS = {u: ["-mllvm", "-disable-machine-licm"] for u in CHAIN_UNITS + TREE_UNITS}
-# the flat scenes' global-cull level kernels (C2's fused camera kernel): the scheduler's AMDGPU register-pressure
-# trackers measured C2 0.1176 -> 0.1166 ms; the same flag on every unit cost C3 and C4 1 % (profiles/r05/ab_trackers.txt)
-UNIT_FLAGS["render_levels_g0_gl.hip"] = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
+# The unit table: logical unit name (the object's and the .resources.json's name, what SOURCES and the tools list) ->
+# (source file in csrc, -D defines, per-unit flags).  A name that is not in the table is a plain file built without
+# either (render.hip, the .cpp units).
+# The level, chain, tree and first-hit kernels come in six (G, LC) variants (G: 2 general, 1 groups, 0 flat; LC: culls
+# staged in LDS or read from global memory), each a unit of its own so they compile in parallel, and once per level-0
+# source: the frame's camera, the listed pixels of adaptive frames' refine pass (render_adapt.hip, namespace
+# rr::listed), the camera table of a batch of views (render_views.hip, namespace rr::views).  One file per kind
+# (unit_<kind>.hip) is compiled once per row with the row's defines (unit_select.inc); a new kind, source or G is a new
+# entry in KINDS / UNIT_SRC / the ranges below, not new files.
+NO_LICM = ["-mllvm", "-disable-machine-licm"]
+TRACKERS = ["-mllvm", "-amdgpu-use-amdgpu-trackers=1"]
+KINDS = ("levels", "chain", "tree", "hit")
+UNIT_SRC = {"": 0, "listed_": 1, "views_": 2}  # infix of the unit's name -> RR_UNIT_SRC
+
+
+def _kind_flags(kind, g, lc):
+    """The flags of a variant, whatever its level-0 source: a listed or views unit is built like the unit it mirrors."""
+    if kind in ("chain", "tree"):
+        # the chain loop (and the tree loop) must not get loop-invariant constants hoisted into registers: they spill
+        # instead of being rematerialised
+        return NO_LICM
+    if kind == "levels" and (g, lc) == (0, "gl"):
+        # the flat scenes' global-cull level kernels (C2's fused camera kernel): the scheduler's AMDGPU register-pressure
+        # trackers measured C2 0.1176 -> 0.1166 ms; the same flag on every unit cost C3 and C4 1 % (profiles/r05/ab_trackers.txt)
+        return TRACKERS
+    return []  # levels otherwise; hit: first-hit walks are not cross-lane (XL off) and need nothing
+
+
+def _variants(src, *kinds):
+    return [f"render_{src}{k}_g{g}_{lc}.hip" for k in kinds for g in (2, 1, 0) for lc in ("lds", "gl")]  # slowest first
+
+
+UNITS = {f"render_{s}{k}_g{g}_{lc}.hip": (f"unit_{k}.hip",
+                                          [f"RR_UNIT_G={g}", f"RR_UNIT_LC={int(lc == 'lds')}", f"RR_UNIT_SRC={n}"],
+                                          _kind_flags(k, g, lc))
+         for s, n in UNIT_SRC.items() for k in KINDS for g in (2, 1, 0) for lc in ("lds", "gl")
+         if (s, k) != ("listed_", "hit")}  # no listed-pixel first-hit query
 # the persistent level-0 loop (render_persist.inc persist_kernel: the C2 frame as one resident launch), built like the
 # unit whose kernel body it shares; its tile loop must not get loop-invariant constants hoisted into registers either
 # (with machine LICM the kernel spills 36 VGPRs at its 4 waves per SIMD; without, none: 125 VGPRs)
+UNITS["render_persist_g0_gl.hip"] = ("render_persist_g0_gl.hip", [], TRACKERS + NO_LICM)
+UNIT_FLAGS = {u: f for u, (_, _, f) in UNITS.items() if f}
+
+LEVEL_UNITS = _variants("", "levels")
 PERSIST_UNITS = ["render_persist_g0_gl.hip"]
-UNIT_FLAGS["render_persist_g0_gl.hip"] = UNIT_FLAGS["render_levels_g0_gl.hip"] + ["-mllvm", "-disable-machine-licm"]
-# first-hit kernels (render_hit.inc hit_kernel: rr_hit_at, rr_render_aov); their walks are not cross-lane (XL off)
-HIT_UNITS = [f"render_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
-# adaptive frames' refine pass (render_adapt.hip): the level, chain and tree kernels compiled once more with the
-# listed-pixel level-0 source (RR_LISTED, namespace rr::listed), each built like the unit it mirrors
-LISTED_UNITS = [f"render_listed_{k}_g{g}_{lc}.hip" for k in ("chain", "tree", "levels") for g in (2, 1, 0) for lc in ("lds", "gl")]
-for _u in LISTED_UNITS:
-    _like = _u.replace("render_listed_", "render_")
-    if _like in UNIT_FLAGS:
-        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-# batches of views (render_views.hip, rr_render_views): the same kernels once more with the camera-table level-0 source
-# (RR_VIEWS, namespace rr::views), each built like the unit it mirrors
-VIEWS_UNITS = [f"render_views_{k}_g{g}_{lc}.hip" for k in ("chain", "tree", "levels") for g in (2, 1, 0) for lc in ("lds", "gl")]
-for _u in VIEWS_UNITS:
-    _like = _u.replace("render_views_", "render_")
-    if _like in UNIT_FLAGS:
-        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
-# first-hit planes of a batch of views (rr_render_views_aov): the first-hit kernels' camera variants with the same
-# camera-table source, each built like the render_hit_g* unit it mirrors
-VIEWS_HIT_UNITS = [f"render_views_hit_g{g}_{lc}.hip" for g in (2, 1, 0) for lc in ("lds", "gl")]
-for _u in VIEWS_HIT_UNITS:
-    _like = _u.replace("render_views_hit_", "render_hit_")
-    if _like in UNIT_FLAGS:
-        UNIT_FLAGS[_u] = UNIT_FLAGS[_like]
+CHAIN_UNITS = _variants("", "chain")
+TREE_UNITS = _variants("", "tree")
+HIT_UNITS = _variants("", "hit")  # rr_hit_at, rr_render_aov
+LISTED_UNITS = _variants("listed_", "chain", "tree", "levels")
+VIEWS_UNITS = _variants("views_", "chain", "tree", "levels")  # rr_render_views
+VIEWS_HIT_UNITS = _variants("views_", "hit")  # rr_render_views_aov
 # device-resident ray queries (rr_camera_rays_device, rr_hit_at_device): the camera-ray and record-writer kernels
 RAYS_UNITS = ["render_rays.hip"]
-SOURCES = LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS + ["render.hip", "render_hit.hip", "render_adapt.hip", "render_views.hip"] + RAYS_UNITS + ["api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp",
-                                         "imgfmt.cpp"]
+SOURCES = (LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS +
+           ["render.hip", "render_adapt.hip", "render_views.hip"] + RAYS_UNITS +
+           ["api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp", "imgfmt.cpp"])
 
 
 def source_digest():
@@ -194,14 +209,22 @@ def check_cross_lane(resource_files):
     return names
 
 
+def unit_command(unit, out, csrc=None, extra=()):
+    """(command, source path): how `unit` is compiled into `out` — the one place that knows.  unit: a name of UNITS, or
+    a plain file of csrc.  csrc: another tree's sources (experiment builds, probes); extra: flags on top of the
+    product's (-D defines, -I of that tree, --cuda-device-only -S of the tools that read assembly)."""
+    src, defines, flags = UNITS.get(unit, (unit, [], []))
+    path = os.path.join(csrc or CSRC, src)
+    cmd = [HIPCC] + (["-x", "hip"] if unit.endswith(".cpp") else []) + COMMON + DEVICE + flags
+    cmd += ["-D" + d for d in defines] + list(extra) + ["-c", path, "-o", out]
+    if unit.endswith(".hip"):
+        cmd += REMARKS
+    return cmd, path
+
+
 def _compile(src, deps, verbose):
     out = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
-    path = os.path.join(CSRC, src)
-    cmd = [HIPCC] + COMMON + DEVICE + UNIT_FLAGS.get(src, []) + ["-c", path, "-o", out]
-    if src.endswith(".cpp"):
-        cmd = [HIPCC, "-x", "hip"] + COMMON + DEVICE + ["-c", path, "-o", out]
-    else:
-        cmd += REMARKS
+    cmd, path = unit_command(src, out)
     key = unit_key(path, unit_deps(path, deps), cmd)
     if _key_matches(out, key) and (src.endswith(".cpp") or os.path.exists(out + ".resources.json")):
         return out
@@ -244,11 +267,8 @@ def build_variant(name, defines, verbose=False, patch=None, extra=None):
 
     def one(src):
         o = os.path.join(out_dir, os.path.splitext(src)[0] + ".o")
-        pre = [HIPCC, "-x", "hip"] if src.endswith(".cpp") else [HIPCC]
         inc = ["-I" + os.path.join(os.path.dirname(os.path.dirname(csrc)), "include")] if patch else []
-        cmd = pre + COMMON + inc + DEVICE + UNIT_FLAGS.get(src, []) + flags + ["-c", os.path.join(csrc, src), "-o", o]
-        if src.endswith(".hip"):
-            cmd += REMARKS + list(extra or [])
+        cmd, _ = unit_command(src, o, csrc, inc + flags + (list(extra or []) if src.endswith(".hip") else []))
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

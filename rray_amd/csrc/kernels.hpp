@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -191,8 +192,23 @@ hipError_t launch_tile_order(const uint32_t* cost, uint32_t* perm, uint32_t* scr
 // trace + shade run as one kernel per level (no transparent material, so no n1/n2 walk between them);
 // those levels finish their reflection chains themselves and need no combine pass
 bool fused_levels(const DevScene& S);
+// The scene's kernel variant: G = 0 flat, 1 groups, 2 general (CSG, 4-entry leaves); LC = culls staged in LDS.
+// dispatch_glc calls f(G, LC) with the pair as std::integral_constant values, so the callee names an instantiation:
+//   dispatch_glc(S, [&](auto g, auto lc) { launch_level_t<g(), lc()>(S, A, st, prof); });
+// Every launch_* that picks a <G, LC> instantiation goes through it.
+template <class F>
+inline void dispatch_glc(const DevScene& S, F&& f) {
+    using std::integral_constant;
+    const int g = S.general ? 2 : S.has_groups ? 1 : 0;
+    if (g == 2)
+        S.lds_culls ? f(integral_constant<int, 2>{}, std::true_type{}) : f(integral_constant<int, 2>{}, std::false_type{});
+    else if (g == 1)
+        S.lds_culls ? f(integral_constant<int, 1>{}, std::true_type{}) : f(integral_constant<int, 1>{}, std::false_type{});
+    else
+        S.lds_culls ? f(integral_constant<int, 0>{}, std::true_type{}) : f(integral_constant<int, 0>{}, std::false_type{});
+}
 // one (G, LC) variant of a level's kernels (render_levels.inc), instantiated in its own translation
-// unit render_levels_g<G>_<lds|gl>.hip; G = 0 flat, 1 groups, 2 general; LC = culls staged in LDS
+// unit render_levels_g<G>_<lds|gl> (unit_levels.hip, compiled once per variant: build.py UNITS)
 template <int G, bool LC>
 void launch_level_t(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof);
 hipError_t launch_combine(const CombArgs& C, hipStream_t stream, KernelProf* prof = nullptr);
@@ -235,7 +251,7 @@ hipError_t launch_shadow_query(const DevScene& S, const double* pts, const doubl
 
 // Adaptive anti-aliasing (render_adapt.hip).  The refine pass renders the samples of a device-side
 // list of pixels (LevelArgs.list) with the level kernels compiled a second time, in namespace rr::listed with
-// RR_LISTED defined (render_listed_g<G>_<lds|gl>.hip): the production instantiations above do not carry the listed
+// RR_LISTED defined (the units render_listed_*_g<G>_<lds|gl>): the production instantiations above do not carry the listed
 // source.  Every production dispatch is served: the fused level 0, the chain kernels and the tree kernels.
 namespace listed {
 template <int G, bool LC>
@@ -250,7 +266,7 @@ hipError_t launch_chain_listed(const DevScene& S, const LevelArgs& A, hipStream_
 hipError_t launch_tree_listed(const DevScene& S, const LevelArgs& A, hipStream_t stream, KernelProf* prof = nullptr);
 // Batches of views (rr_render_views): many cameras of one scene in one launch per pass.  The level,
 // chain and tree kernels compiled a third time, in namespace rr::views with RR_VIEWS defined
-// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip): level-0 events come from the camera table LevelArgs.views.
+// (the units render_views_{levels,chain,tree}_g<G>_<lds|gl>): level-0 events come from the camera table LevelArgs.views.
 // The production and listed instantiations do not carry the source.  launch_*_views (render_views.hip) pick the
 // scene's (G, LC) variant as launch_level / launch_chain / launch_tree do.
 namespace views {
@@ -311,7 +327,7 @@ template <int G, bool LC>
 void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
 hipError_t launch_hit(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
 // First-hit planes of a batch of views (rr_render_views_aov): hit_kernel's camera variants compiled
-// once more in namespace rr::views (render_views_hit_g<G>_<lds|gl>.hip).  One pass of whole views per launch: A.views
+// once more in namespace rr::views (the units render_views_hit_g<G>_<lds|gl>).  One pass of whole views per launch: A.views
 // and O's planes start at the pass's first view, A.n = the pass's views * A.view_e, A.base 0, no cached bundles.
 namespace views {
 template <int G, bool LC>

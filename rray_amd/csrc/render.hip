@@ -298,23 +298,7 @@ bool fused_levels(const DevScene& S) { return !S.has_transparent && !std::getenv
 
 hipError_t launch_level(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0;  // G: flat / groups / general (CSG, 4-entry leaves)
-    if (g == 2) {
-        if (S.lds_culls)
-            launch_level_t<2, true>(S, A, st, prof);
-        else
-            launch_level_t<2, false>(S, A, st, prof);
-    } else if (g == 1) {
-        if (S.lds_culls)
-            launch_level_t<1, true>(S, A, st, prof);
-        else
-            launch_level_t<1, false>(S, A, st, prof);
-    } else {
-        if (S.lds_culls)
-            launch_level_t<0, true>(S, A, st, prof);
-        else
-            launch_level_t<0, false>(S, A, st, prof);
-    }
+    dispatch_glc(S, [&](auto g, auto lc) { launch_level_t<g(), lc()>(S, A, st, prof); });
     return hipGetLastError();
 }
 
@@ -324,23 +308,7 @@ bool chain_levels(const DevScene& S, int max_children, int max_depth) {
 
 hipError_t launch_chain(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof, bool deep) {
     if (A.n <= 0) return hipSuccess;
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0;
-    if (g == 2) {
-        if (S.lds_culls)
-            launch_chain_t<2, true>(S, A, st, prof, deep);
-        else
-            launch_chain_t<2, false>(S, A, st, prof, deep);
-    } else if (g == 1) {
-        if (S.lds_culls)
-            launch_chain_t<1, true>(S, A, st, prof, deep);
-        else
-            launch_chain_t<1, false>(S, A, st, prof, deep);
-    } else {
-        if (S.lds_culls)
-            launch_chain_t<0, true>(S, A, st, prof, deep);
-        else
-            launch_chain_t<0, false>(S, A, st, prof, deep);
-    }
+    dispatch_glc(S, [&](auto g, auto lc) { launch_chain_t<g(), lc()>(S, A, st, prof, deep); });
     return hipGetLastError();
 }
 
@@ -348,23 +316,14 @@ bool tree_levels(const DevScene& S) { return S.has_transparent && !std::getenv("
 
 hipError_t launch_tree(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0;
-    if (g == 2) {
-        if (S.lds_culls)
-            launch_tree_t<2, true>(S, A, st, prof);
-        else
-            launch_tree_t<2, false>(S, A, st, prof);
-    } else if (g == 1) {
-        if (S.lds_culls)
-            launch_tree_t<1, true>(S, A, st, prof);
-        else
-            launch_tree_t<1, false>(S, A, st, prof);
-    } else {
-        if (S.lds_culls)
-            launch_tree_t<0, true>(S, A, st, prof);
-        else
-            launch_tree_t<0, false>(S, A, st, prof);
-    }
+    dispatch_glc(S, [&](auto g, auto lc) { launch_tree_t<g(), lc()>(S, A, st, prof); });
+    return hipGetLastError();
+}
+
+// the first-hit kernels (render_hit.inc hit_kernel), instantiated in the units render_hit_g<G>_<lds|gl>
+hipError_t launch_hit(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
+    if (A.n <= 0) return hipSuccess;
+    dispatch_glc(S, [&](auto g, auto lc) { launch_hit_t<g(), lc()>(S, A, O, st); });
     return hipGetLastError();
 }
 
@@ -405,23 +364,7 @@ static void launch_shadow_query_t(const DevScene& S, const double* pts, const do
 hipError_t launch_shadow_query(const DevScene& S, const double* pts, const double* lps, int64_t n, int32_t* out,
                                unsigned long long* counters, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0;
-    if (g == 2) {
-        if (S.lds_culls)
-            launch_shadow_query_t<2, true>(S, pts, lps, n, out, counters, st);
-        else
-            launch_shadow_query_t<2, false>(S, pts, lps, n, out, counters, st);
-    } else if (g == 1) {
-        if (S.lds_culls)
-            launch_shadow_query_t<1, true>(S, pts, lps, n, out, counters, st);
-        else
-            launch_shadow_query_t<1, false>(S, pts, lps, n, out, counters, st);
-    } else {
-        if (S.lds_culls)
-            launch_shadow_query_t<0, true>(S, pts, lps, n, out, counters, st);
-        else
-            launch_shadow_query_t<0, false>(S, pts, lps, n, out, counters, st);
-    }
+    dispatch_glc(S, [&](auto g, auto lc) { launch_shadow_query_t<g(), lc()>(S, pts, lps, n, out, counters, st); });
     return hipGetLastError();
 }
 

@@ -3,8 +3,8 @@
 //   adapt_scan_kernel     exclusive scan of the per-block counts; the totals, left on the device
 //   adapt_scatter_kernel  the refined pixels' indices in ascending raster order (ballot + popcount in the wave)
 //   adapt_resolve_kernel  canvas.rs:85-96 over each listed pixel's aa x aa samples, written over its aa 1 colour
-// and the dispatch of the refine pass to the listed-pixel level kernels (namespace rr::listed,
-// render_listed_*.hip).  Everything runs on the caller's stream; no count ever visits the host, and the list's order
+// and the dispatch of the refine pass to the listed-pixel level kernels (namespace rr::listed: the units
+// render_listed_*_g<G>_<lds|gl>, unit_*.hip compiled with the listed source).  Everything runs on the caller's stream; no count ever visits the host, and the list's order
 // does not depend on which block runs first, so the refine pass's waves hold the same samples in every run.
 #include <algorithm>
 #include <cstdlib>
@@ -136,45 +136,25 @@ hipError_t launch_adapt_resolve(const AdaptArgs& P, hipStream_t st) {
 }
 
 // the refine pass's level-0 launch, by the scene's kernel family as launch_level / launch_chain / launch_tree
-#define RR_LISTED_DISPATCH(CALL)                     \
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0; \
-    if (g == 2) {                                    \
-        if (S.lds_culls)                             \
-            listed::CALL(2, true);                   \
-        else                                         \
-            listed::CALL(2, false);                  \
-    } else if (g == 1) {                             \
-        if (S.lds_culls)                             \
-            listed::CALL(1, true);                   \
-        else                                         \
-            listed::CALL(1, false);                  \
-    } else {                                         \
-        if (S.lds_culls)                             \
-            listed::CALL(0, true);                   \
-        else                                         \
-            listed::CALL(0, false);                  \
-    }                                                \
-    return hipGetLastError()
-
 hipError_t launch_level_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!A.list || !A.n_dev || A.level != 0 || !fused_levels(S)) return hipErrorInvalidValue;
-#define RR_CALL_LEVEL(G, LC) launch_level_t<G, LC>(S, A, st, prof)
-    RR_LISTED_DISPATCH(RR_CALL_LEVEL);
+    dispatch_glc(S, [&](auto g, auto lc) { listed::launch_level_t<g(), lc()>(S, A, st, prof); });
+    return hipGetLastError();
 }
 
 hipError_t launch_chain_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!A.list || !A.n_dev || A.level != 0) return hipErrorInvalidValue;
-#define RR_CALL_CHAIN(G, LC) launch_chain_t<G, LC>(S, A, st, prof, false)
-    RR_LISTED_DISPATCH(RR_CALL_CHAIN);
+    dispatch_glc(S, [&](auto g, auto lc) { listed::launch_chain_t<g(), lc()>(S, A, st, prof, false); });
+    return hipGetLastError();
 }
 
 hipError_t launch_tree_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!A.list || !A.n_dev || A.level != 0) return hipErrorInvalidValue;
-#define RR_CALL_TREE(G, LC) launch_tree_t<G, LC>(S, A, st, prof)
-    RR_LISTED_DISPATCH(RR_CALL_TREE);
+    dispatch_glc(S, [&](auto g, auto lc) { listed::launch_tree_t<g(), lc()>(S, A, st, prof); });
+    return hipGetLastError();
 }
 
 }  // namespace rr

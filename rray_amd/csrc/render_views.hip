@@ -1,31 +1,12 @@
 // render_views.hip — the launches of a batch of views (rr_render_views): one pass's level-0 events
 // through the scene's own in-wave kernel family, compiled with the camera-table source in namespace rr::views
-// (render_views_{levels,chain,tree}_g<G>_<lds|gl>.hip), and a pass of rr_render_views_aov (§3.17) through the first-hit
-// kernel compiled the same way (render_views_hit_g<G>_<lds|gl>.hip).  Only the (G, LC) dispatch lives here.
+// (the units render_views_{levels,chain,tree}_g<G>_<lds|gl>: unit_*.hip with the views source), and a pass of
+// rr_render_views_aov (§3.17) through the first-hit kernel compiled the same way (render_views_hit_g<G>_<lds|gl>).
+// Only the argument checks and the (G, LC) dispatch (kernels.hpp dispatch_glc) live here: the pass's level-0 launch,
+// by the scene's kernel family as launch_level / launch_chain / launch_tree.
 #include "kernels.hpp"
 
 namespace rr {
-
-// the pass's level-0 launch, by the scene's kernel family as launch_level / launch_chain / launch_tree
-#define RR_VIEWS_DISPATCH(CALL)                         \
-    const int g = S.general ? 2 : S.has_groups ? 1 : 0; \
-    if (g == 2) {                                       \
-        if (S.lds_culls)                                \
-            views::CALL(2, true);                       \
-        else                                            \
-            views::CALL(2, false);                      \
-    } else if (g == 1) {                                \
-        if (S.lds_culls)                                \
-            views::CALL(1, true);                       \
-        else                                            \
-            views::CALL(1, false);                      \
-    } else {                                            \
-        if (S.lds_culls)                                \
-            views::CALL(0, true);                       \
-        else                                            \
-            views::CALL(0, false);                      \
-    }                                                   \
-    return hipGetLastError()
 
 // what every rr::views kernel relies on: a camera table, whole waves per view, level 0, camera rays, none of the
 // single frame's per-camera tables (cached bundles, cost order, pixel waves, the resident loop's queue)
@@ -38,33 +19,33 @@ static bool views_args_ok(const LevelArgs& A) {
 hipError_t launch_level_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!views_args_ok(A) || !fused_levels(S)) return hipErrorInvalidValue;
-#define RR_CALL_LEVEL(G, LC) launch_level_t<G, LC>(S, A, st, prof)
-    RR_VIEWS_DISPATCH(RR_CALL_LEVEL);
+    dispatch_glc(S, [&](auto g, auto lc) { views::launch_level_t<g(), lc()>(S, A, st, prof); });
+    return hipGetLastError();
 }
 
 hipError_t launch_chain_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!views_args_ok(A)) return hipErrorInvalidValue;
-#define RR_CALL_CHAIN(G, LC) launch_chain_t<G, LC>(S, A, st, prof, false)
-    RR_VIEWS_DISPATCH(RR_CALL_CHAIN);
+    dispatch_glc(S, [&](auto g, auto lc) { views::launch_chain_t<g(), lc()>(S, A, st, prof, false); });
+    return hipGetLastError();
 }
 
 hipError_t launch_tree_views(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
     if (!views_args_ok(A)) return hipErrorInvalidValue;
-#define RR_CALL_TREE(G, LC) launch_tree_t<G, LC>(S, A, st, prof)
-    RR_VIEWS_DISPATCH(RR_CALL_TREE);
+    dispatch_glc(S, [&](auto g, auto lc) { views::launch_tree_t<g(), lc()>(S, A, st, prof); });
+    return hipGetLastError();
 }
 
-// one pass of rr_render_views_aov: the first-hit kernel over the pass's views (render_views_hit_g<G>_<lds|gl>.hip).
+// one pass of rr_render_views_aov: the first-hit kernel over the pass's views (the units render_views_hit_g<G>_<lds|gl>).
 // It counts into the query buffer and clears nothing (no counters_zero); the planes it writes are the ones O names
 hipError_t launch_hit_views(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
     if (A.n <= 0) return hipSuccess;
     if (!views_args_ok(A) || A.base != 0 || A.n >= ((int64_t)1 << 31) || A.counters_zero || !O.node_object ||
         !(O.depth || O.normal || O.object || O.albedo))
         return hipErrorInvalidValue;
-#define RR_CALL_HIT(G, LC) launch_hit_t<G, LC>(S, A, O, st)
-    RR_VIEWS_DISPATCH(RR_CALL_HIT);
+    dispatch_glc(S, [&](auto g, auto lc) { views::launch_hit_t<g(), lc()>(S, A, O, st); });
+    return hipGetLastError();
 }
 
 }  // namespace rr

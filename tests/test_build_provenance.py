@@ -96,11 +96,7 @@ def test_in_tree_objects_carry_keys_of_the_current_sources():
     deps = B._dep_files()
     for src in B.SOURCES:
         out = os.path.join(B.OBJ, os.path.splitext(src)[0] + ".o")
-        path = os.path.join(B.CSRC, src)
-        if src.endswith(".cpp"):
-            cmd = [B.HIPCC, "-x", "hip"] + B.COMMON + B.DEVICE + ["-c", path, "-o", out]
-        else:
-            cmd = [B.HIPCC] + B.COMMON + B.DEVICE + B.UNIT_FLAGS.get(src, []) + ["-c", path, "-o", out] + B.REMARKS
+        cmd, path = B.unit_command(src, out)
         assert B._key_matches(out, B.unit_key(path, B.unit_deps(path, deps), cmd)), src
 
 
@@ -118,7 +114,7 @@ def test_unit_deps_follow_includes(tmp_path):
     assert B.unit_deps(str(u), cands) == sorted(cands)
     # the product: the chain units depend on the device code, the PNG writer does not
     deps = B._dep_files()
-    chain = B.unit_deps(os.path.join(B.CSRC, "render_chain_g0_gl.hip"), deps)
+    chain = B.unit_deps(os.path.join(B.CSRC, "unit_chain.hip"), deps)
     assert any(d.endswith("device_core.inc") for d in chain)
     png = B.unit_deps(os.path.join(B.CSRC, "png.cpp"), deps)
     assert not any(d.endswith("device_core.inc") for d in png)

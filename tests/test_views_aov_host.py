@@ -45,14 +45,18 @@ def test_symbols_are_declared_exported_and_bound(R):
     assert len(L.rr_render_views_aov.argtypes) == 10 and len(L.rr_render_views_aov_device.argtypes) == 10
     for n in ("render_views_aov", "render_views_aov_device"):
         assert callable(getattr(R.Renderer, n))
-    # the six units are part of the build, each built like the first-hit unit it mirrors
+    # the six units are part of the build, each built like the first-hit unit it mirrors: the same source file and
+    # flags, and of the defines only the level-0 source differs
     from rray_amd import build
 
     for g in (0, 1, 2):
         for lc in ("lds", "gl"):
-            u = f"render_views_hit_g{g}_{lc}.hip"
-            assert u in build.SOURCES and os.path.exists(os.path.join(CSRC, u)), u
-            assert build.UNIT_FLAGS.get(u, []) == build.UNIT_FLAGS.get(f"render_hit_g{g}_{lc}.hip", []), u
+            u, like = f"render_views_hit_g{g}_{lc}.hip", f"render_hit_g{g}_{lc}.hip"
+            assert u in build.SOURCES and like in build.SOURCES, u
+            (src, defs, flags), (src_l, defs_l, flags_l) = build.UNITS[u], build.UNITS[like]
+            assert flags == flags_l, u
+            assert src == src_l and os.path.exists(os.path.join(CSRC, src)), u
+            assert set(defs) ^ set(defs_l) == {"RR_UNIT_SRC=2", "RR_UNIT_SRC=0"}, u
 
 
 def test_bad_arguments_are_refused_without_a_device(R):

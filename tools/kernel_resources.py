@@ -18,8 +18,7 @@ KEYS = ["VGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "Occu
 
 def resources(src, defines):
     # built as build.py builds the unit (its per-unit flags decide spills: the persistent loop's unit, the C2 unit)
-    cmd = [B.HIPCC] + B.COMMON + B.DEVICE + B.UNIT_FLAGS.get(src, []) + ["-D" + d for d in defines] + [
-        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(B.CSRC, src), "-o", os.devnull]
+    cmd, _ = B.unit_command(src, os.devnull, extra=["-D" + d for d in defines] + ["--cuda-device-only"])
     r = subprocess.run(cmd, capture_output=True, text=True)
     out, cur = {}, None
     for line in r.stderr.splitlines():

@@ -21,9 +21,8 @@ def main():
         csrc = os.path.join(td, "rray_amd", "csrc")
         for f, script in zip(edits[::2], edits[1::2]):
             subprocess.run(["sed", "-i", script, os.path.join(csrc, f)], check=True)
-        common = [c if not c.startswith("-I") else "-I" + os.path.join(td, "include") for c in B.COMMON]
-        cmd = [B.HIPCC] + common + B.DEVICE + B.UNIT_FLAGS.get(unit, []) + B.REMARKS + [
-            "-c", os.path.join(csrc, unit), "-o", os.path.join(td, "x.o")]
+        cmd, _ = B.unit_command(unit, os.path.join(td, "x.o"), csrc)
+        cmd = [c if not c.startswith("-I") else "-I" + os.path.join(td, "include") for c in cmd]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             print(r.stderr[-3000:])

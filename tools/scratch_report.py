@@ -16,8 +16,7 @@ from rray_amd import build as B  # noqa: E402
 
 def assemble(unit, out_dir):
     out = os.path.join(out_dir, unit.replace(".hip", ".s"))
-    cmd = [B.HIPCC] + B.COMMON + B.DEVICE + B.UNIT_FLAGS.get(unit, []) + ["--cuda-device-only", "-S",
-                                                                          os.path.join(B.CSRC, unit), "-o", out]
+    cmd, _ = B.unit_command(unit, out, extra=["--cuda-device-only", "-S"])  # -S wins over the command's -c
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stderr)
