@@ -448,6 +448,39 @@ int rr_hit_at_device(rr_ctx* ctx, int64_t n, const void* d_rays, void* d_hits, v
 int rr_is_shadowed_device(rr_ctx* ctx, int64_t n, const void* d_points, const void* d_light_positions, void* d_out,
                           void* hip_stream);
 
+/* ---- ordered ray batches (additive to ABI 11; test RR_HAS_RAY_ORDER) ----
+ * Device ray batches are incoherent by nature (lens samples, proposed rays, picking rays), and a wave of 64 unrelated
+ * rays culls nothing.  One call puts a batch into a coherent order and the two ordered queries walk the batch in that
+ * order; they still answer ray i in slot i, bit for bit what the plain entries write.
+ * rr_ray_order_device: writes n uint32 to d_perm; d_perm[j] is the index of the ray at position j of the order.  Needs
+ *   no scene.  Deterministic: d_perm == argsort(keys, stable) with the 32-bit keys of rray_amd.ray_order_keys — bounds of
+ *   ox, oy, oz and of the octahedral direction (u, v) over the batch's valid rays, six bits per origin axis and seven
+ *   per direction axis, morton3(origin) << 14 | morton2(direction); a ray with a NaN or infinite component or a zero
+ *   direction has the key 0xFFFFFFFF and sorts to the end.  Directions need not be normalised.
+ * rr_color_at_device_ordered / rr_hit_at_device_ordered: the plain entries with wave slot t working on ray d_perm[t].
+ *   d_rgb[i] / d_hits[i] are what rr_color_at_device / rr_hit_at_device write for the same batch, bit for bit; ray
+ *   d_perm[t]'s area-light jitter identity is sample d_perm[t], path 1.  (One value of the plain entries themselves
+ *   depends on which rays share a wave: in a wave that mixes shininess values, the lanes whose shininess is not the
+ *   wave's first lane's take the library pow instead of the correctly rounded one, so a specular term may move by an
+ *   ulp with the batch's order — between two plain calls as well.  Hits never do.)  d_perm == NULL: the library computes the order
+ *   itself into context-owned scratch, then traces, all on the caller's stream.  A non-null d_perm (from
+ *   rr_ray_order_device or the caller's own) must hold each of 0..n-1 exactly once.  It is NOT CHECKED: an index >= n
+ *   reads and writes out of bounds, a repeated index leaves some slot unwritten.
+ * Stream claim, device guard, refusals, n == 0, the n < 2^32 limit, NaN-ray reporting and rr_last_stats are the plain
+ * device entries' (rr_ray_order_device refuses a null ctx / buffer, n < 0, n >= 2^32 and a multi-device or virtual
+ * context, and leaves rr_last_stats alone).  rr_last_stats after an ordered query: the same rays, shadow_rays,
+ * shade_events, n1n2_scans, samples and nan_rays as after the plain call; prim_tests, exact_flops and wave_visits are
+ * reproducible but differ — fewer wave visits is what the order is for.  The hit query runs in passes of at most
+ * min(context batch, 2^22) positions of the order.  RR_E_ARG under RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN: the
+ * ordered colour query is served by the in-wave kernels only.  RR_E_HIP: the scratch (about 16 bytes per ray, grown
+ * on demand, freed with the context) could not be allocated.  Frame state is left alone, as by the plain entries. */
+#define RR_HAS_RAY_ORDER 1
+int rr_ray_order_device(rr_ctx* ctx, int64_t n, const void* d_rays, void* d_perm, void* hip_stream);
+int rr_color_at_device_ordered(rr_ctx* ctx, int64_t n, const void* d_rays, const void* d_perm, int32_t remaining,
+                               uint64_t seed, int32_t jitter_mode, void* d_rgb, void* hip_stream);
+int rr_hit_at_device_ordered(rr_ctx* ctx, int64_t n, const void* d_rays, const void* d_perm, void* d_hits,
+                             void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

@@ -10,6 +10,7 @@ from .render import (  # noqa: F401
     Renderer,
     SceneBuilder,
     adaptive_mask,
+    ray_order_keys,
     balance_bands,
     YamlScene,
     camera,
@@ -25,5 +26,5 @@ from .render import (  # noqa: F401
 )
 
 __all__ = ["Renderer", "SceneBuilder", "YamlScene", "camera", "part_rows", "quantize", "write_png",
-           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "RRError",
+           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "ray_order_keys", "RRError",
            "lib"]

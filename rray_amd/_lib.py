@@ -82,7 +82,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_group_set_bands", "rr_hit_at", "rr_render_aov", "rr_render_aov_device", "rr_render_adaptive",
            "rr_render_adaptive_device", "rr_resident_launch", "rr_render_views", "rr_render_views_device",
            "rr_render_views_aov", "rr_render_views_aov_device", "rr_camera_rays_device", "rr_color_at_device",
-           "rr_hit_at_device", "rr_is_shadowed_device"]
+           "rr_hit_at_device", "rr_is_shadowed_device", "rr_ray_order_device", "rr_color_at_device_ordered",
+           "rr_hit_at_device_ordered"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -189,6 +190,11 @@ def lib():
                                      C.c_void_p]
     L.rr_hit_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rr_is_shadowed_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # ordered ray batches (RR_HAS_RAY_ORDER)
+    L.rr_ray_order_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rr_color_at_device_ordered.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
+                                             C.c_int32, C.c_void_p, C.c_void_p]
+    L.rr_hit_at_device_ordered.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -84,6 +84,9 @@ struct rr_ctx {
     // rr_is_shadowed_device's walk counters: a sink nobody reads, so that the query leaves pending stats (which may be
     // the query buffer's) as they are
     DBuf shadow_sink;
+    // ordered ray batches (rr_ray_order_device, rr_*_at_device_ordered): the sort's scratch (rr::ray_order_scratch_bytes)
+    // and the order of a call that brings none (d_perm == NULL); grow on demand, freed with the context
+    DBuf order_scratch, order_perm;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -423,7 +426,8 @@ rr::FramePlan plan_run(const rr_ctx* c, const FrameFacts& facts, const rr::Level
     r.aa = A.aa;
     r.block_rows = A.block_rows;
     r.rays0 = A.rays0 != nullptr;
-    r.listed = A.list != nullptr;
+    r.listed = A.list != nullptr && !A.rays0;
+    r.ordered = A.list != nullptr && A.rays0 != nullptr;  // the listed kernels' second source: an ordered ray batch
     r.pw = A.pw != 0;
     r.pw_rows = A.pw_rows;
     r.pw_wpb = A.pw_wpb;
@@ -905,7 +909,7 @@ void rr_destroy(rr_ctx* c) {
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
-                    &c->shadow_sink})
+                    &c->shadow_sink, &c->order_scratch, &c->order_perm})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2033,6 +2037,127 @@ int rr_hit_at_device(rr_ctx* c, int64_t n, const void* d_rays, void* d_hits, voi
         set_level0_index(A);
         HIPCHK(rr::launch_hit(c->S, A, O, st));
         HIPCHK(rr::launch_hit_records(O, np, static_cast<char*>(d_hits) + sizeof(rr_hit) * (size_t)first, st));
+    }
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n);
+    return RR_OK;
+}
+
+// ---- ordered ray batches (render_order.inc) ----
+// The order of a batch is a permutation on the device; the two ordered queries walk the batch in it and answer ray i in
+// slot i, as the plain entries do.  The isolation rule above holds for all three.
+static int order_into(rr_ctx* c, int64_t n, const void* d_rays, uint32_t* perm, hipStream_t st) {
+    HIPCHK(c->order_scratch.ensure(rr::ray_order_scratch_bytes(n)));
+    HIPCHK(rr::launch_ray_order(static_cast<const double*>(d_rays), n, perm, c->order_scratch.p, st));
+    return RR_OK;
+}
+// the order an ordered query walks: the caller's, or the library's own into the context's buffer (on st)
+static int order_for(rr_ctx* c, int64_t n, const void* d_rays, const void* d_perm, hipStream_t st, const uint32_t** perm) {
+    *perm = static_cast<const uint32_t*>(d_perm);
+    if (d_perm) return RR_OK;
+    HIPCHK(c->order_perm.ensure((size_t)n * sizeof(uint32_t)));
+    *perm = c->order_perm.as<uint32_t>();
+    return order_into(c, n, d_rays, c->order_perm.as<uint32_t>(), st);
+}
+
+int rr_ray_order_device(rr_ctx* c, int64_t n, const void* d_rays, void* d_perm, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "device-resident ray queries need a single-device context (no multi-device or virtual context)");
+    if (n < 0) return fail(RR_E_ARG, "n is negative");
+    if (n > 0 && (!d_rays || !d_perm)) return fail(RR_E_ARG, "null device buffer");
+    if (n >= ((int64_t)1 << 32)) return fail(RR_E_LIMIT, "a ray batch must hold fewer than 2^32 rays");
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    int rc = order_into(c, n, d_rays, static_cast<uint32_t*>(d_perm), st);
+    if (rc != RR_OK) return rc;
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+int rr_color_at_device_ordered(rr_ctx* c, int64_t n, const void* d_rays, const void* d_perm, int32_t remaining,
+                               uint64_t seed, int32_t jitter_mode, void* d_rgb, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = rays_check(c, n, !d_rays || !d_rgb);
+    if (rc != RR_OK) return rc;
+    if (remaining < 0 || remaining > RR_MAX_DEPTH) return fail(RR_E_LIMIT, "remaining out of range");
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    const uint32_t* perm = nullptr;
+    rc = order_for(c, n, d_rays, d_perm, st, &perm);
+    if (rc != RR_OK) return rc;
+    const int saved_epoch = c->epoch;
+    c->epoch = 2;  // the query buffer (frame buffers keep their state)
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));
+    rr::LevelArgs A{};  // rr_color_at_device's level 0 with slot t on ray perm[t]: its jitter identity is (perm[t], path 1)
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.rays0 = static_cast<const double*>(d_rays);
+    A.list = perm;
+    A.seed = seed;
+    A.jitter_mode = jitter_mode;
+    rc = run_levels(c, frame_facts(c, remaining), A, n, remaining, static_cast<double*>(d_rgb), st);
+    c->epoch = saved_epoch;
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n);
+    return RR_OK;
+}
+
+int rr_hit_at_device_ordered(rr_ctx* c, int64_t n, const void* d_rays, const void* d_perm, void* d_hits,
+                             void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = rays_check(c, n, !d_rays || !d_hits);
+    if (rc != RR_OK) return rc;
+    if (n == 0) return RR_OK;
+    const rr::RayPassPlan plan = rr::plan_ray_passes(n, c->batch);
+    HIPCHK(hipSetDevice(c->device));
+    const size_t d_bytes = (size_t)plan.pass * rr::RR_HIT_DOUBLES * sizeof(double);
+    HIPCHK(c->hitrec.ensure(d_bytes + (size_t)plan.pass * 2 * sizeof(int32_t)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    const uint32_t* perm = nullptr;
+    rc = order_for(c, n, d_rays, d_perm, st, &perm);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.rec_d = c->hitrec.as<double>();
+    O.rec_i = reinterpret_cast<int32_t*>(c->hitrec.as<char>() + d_bytes);
+    O.stride = plan.pass;
+    rr::LevelArgs A{};
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.nseg = A.nseg_out = 1;
+    A.counters = frame_counters(c, 2);
+    A.base = 0;
+    A.rays0 = static_cast<const double*>(d_rays);  // the whole batch: a pass's slots read rays anywhere in it
+    for (int64_t first = 0; first < n; first += plan.pass) {  // a pass: positions [first, first + np) of the order
+        const int64_t np = std::min<int64_t>(plan.pass, n - first);
+        A.list = perm + first;
+        A.n = np;
+        set_level0_index(A);
+        HIPCHK(rr::launch_hit_ordered(c->S, A, O, st));
+        HIPCHK(rr::launch_hit_records_ordered(O, np, perm + first, d_hits, st));
     }
     HIPCHK(hipEventRecord(c->e1, st));
     HIPCHK(claim.release());

@@ -133,6 +133,9 @@ struct FrameRequest {
     // view_events(hs, lrows) level-0 events (total = views * view_e).  0: a single frame.  Last, value-initialised.
     int32_t views{};
     int64_t view_e{};
+    // an ordered ray batch (rr_color_at_device_ordered): with rays0, level-0 slot t works on ray
+    // perm[t]; served by the listed kernels, which hold the in-wave families only.  Last, value-initialised.
+    bool ordered{};
 };
 
 // level-0 events of one view of a batch: its samples rounded up to whole waves, so a wave never holds two views
@@ -260,6 +263,17 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
         f.msg = "internal: the listed-pixel pass needs one batch of a production kernel family";
         return f;
     }
+    // an ordered ray batch: any number of batches, the in-wave kernels only
+    if (r.ordered && (!r.rays0 || r.listed || r.views > 0 || r.pw || r.box_avg)) {
+        f.err = RR_E_ARG;
+        f.msg = "internal: an ordered ray batch is the caller's rays and nothing else";
+        return f;
+    }
+    if (r.ordered && !one_level) {
+        f.err = RR_E_ARG;
+        f.msg = "ordered ray batches are not served by the per-level paths (RRAY_UNFUSED / RRAY_NO_TREE / RRAY_NO_CHAIN)";
+        return f;
+    }
     // a batch of views: passes of whole views through the in-wave kernels, one launch each.  No per-camera state of
     // the context serves it: no cached bundles, no cost order, no resident loop, no deep queue, no pixel waves
     if (r.views > 0) {
@@ -304,7 +318,7 @@ inline FramePlan plan_frame(const FrameTraits& t, const FrameSwitches& sw, const
     // deep chains: frames whose samples are delivered one by one (not the in-wave AA average).  Opt-in: on C3 the
     // deep launch took 1.85 ms for what the camera waves did in 1.54 — the deep rays' walks are latency-bound
     // whether their waves are full or not
-    f.spill = f.family == Family::Chain && r.aa_wave == 0 && !r.pw && !r.listed && r.views == 0 && r.max_depth >= RR_DEEP_FROM && sw.deep;
+    f.spill = f.family == Family::Chain && r.aa_wave == 0 && !r.pw && !r.listed && !r.ordered && r.views == 0 && r.max_depth >= RR_DEEP_FROM && sw.deep;
     f.deep_seg_cap = (int64_t)256 << RR_DEEP_SHIFT;
     f.deep_nseg = (((f.B + 255) / 256) + (1 << RR_DEEP_SHIFT) - 1) >> RR_DEEP_SHIFT;
     // cost-ordered level-0 tiles: one-batch frames of full 8x8 tiles whose level 0 is the whole frame (no

@@ -95,6 +95,8 @@ struct LevelArgs {
     // sample i % aa^2 (dy outer, dx inner) of output pixel list[i / aa^2] (row-major index into the list_w-wide
     // frame); n_dev holds the live event count (aa^2 x the listed pixels), the launch covers the capacity.  Last in
     // the struct, so that no other field moves in the kernels that never read them.
+    // (with rays0, the rr::listed kernels read list as the order of an ordered ray batch instead, DESIGN.md §3.19: level-0
+    // slot base + i works on ray list[base + i], n_dev null and n the host's count)
     const uint32_t* list;
     uint32_t list_w;
     // the flat fused level-0 kernels (shade_body.inc UH): the scalar path for hit-uniform tiles, planes' normals from
@@ -343,5 +345,22 @@ hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, doub
 // hit_records_kernel: the first n entries of hit_kernel's ray-batch planes (O.rec_i / O.rec_d, O.stride entries per
 // plane) as n rr_hit records at `out`; n <= 2^24 (one pass of rr_hit_at_device holds at most 2^22).
 hipError_t launch_hit_records(const HitOut& O, int64_t n, void* out, hipStream_t stream);
+
+// Ordered ray batches (render_order.inc in render_rays.hip).
+// launch_ray_order: perm = argsort(key, stable) of the n (< 2^32) rays at `rays` (six doubles each), key the 32-bit
+// origin-major Morton code of rray_amd.ray_order_keys (bounds over the batch's valid rays, then 6 + 6 + 6 origin bits
+// over 7 + 7 octahedral direction bits; 0xFFFFFFFF for a ray with a non-finite component or no direction).  Five kernels
+// and four 8-bit stable radix passes, all on `stream`.  scratch: ray_order_scratch_bytes(n) bytes the call owns while it runs.
+size_t ray_order_scratch_bytes(int64_t n);
+hipError_t launch_ray_order(const double* rays, int64_t n, uint32_t* perm, void* scratch, hipStream_t stream);
+// the first-hit kernel's ray-batch instantiation with the listed source (in the units render_listed_levels_g<G>_<lds|gl>): slot j
+// of the pass (A.base 0, A.n slots) works on ray A.rays0[A.list[j]] and writes its planes at slot j
+namespace listed {
+template <int G, bool LC>
+void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+}  // namespace listed
+hipError_t launch_hit_ordered(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t stream);
+// hit_records_kernel with a scattered destination: the record of pass slot j goes to out + 192 * perm[j], whole
+hipError_t launch_hit_records_ordered(const HitOut& O, int64_t n, const uint32_t* perm, void* out, hipStream_t stream);
 
 }  // namespace rr

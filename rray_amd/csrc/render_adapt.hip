@@ -135,24 +135,25 @@ hipError_t launch_adapt_resolve(const AdaptArgs& P, hipStream_t st) {
     return hipGetLastError();
 }
 
-// the refine pass's level-0 launch, by the scene's kernel family as launch_level / launch_chain / launch_tree
+// the refine pass's level-0 launch, by the scene's kernel family as launch_level / launch_chain / launch_tree; an
+// ordered ray batch (A.rays0 with A.list its permutation) takes the same launches with a host count
 hipError_t launch_level_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
-    if (!A.list || !A.n_dev || A.level != 0 || !fused_levels(S)) return hipErrorInvalidValue;
+    if (!A.list || (!A.n_dev && !A.rays0) || A.level != 0 || !fused_levels(S)) return hipErrorInvalidValue;
     dispatch_glc(S, [&](auto g, auto lc) { listed::launch_level_t<g(), lc()>(S, A, st, prof); });
     return hipGetLastError();
 }
 
 hipError_t launch_chain_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
-    if (!A.list || !A.n_dev || A.level != 0) return hipErrorInvalidValue;
+    if (!A.list || (!A.n_dev && !A.rays0) || A.level != 0) return hipErrorInvalidValue;
     dispatch_glc(S, [&](auto g, auto lc) { listed::launch_chain_t<g(), lc()>(S, A, st, prof, false); });
     return hipGetLastError();
 }
 
 hipError_t launch_tree_listed(const DevScene& S, const LevelArgs& A, hipStream_t st, KernelProf* prof) {
     if (A.n <= 0) return hipSuccess;
-    if (!A.list || !A.n_dev || A.level != 0) return hipErrorInvalidValue;
+    if (!A.list || (!A.n_dev && !A.rays0) || A.level != 0) return hipErrorInvalidValue;
     dispatch_glc(S, [&](auto g, auto lc) { listed::launch_tree_t<g(), lc()>(S, A, st, prof); });
     return hipGetLastError();
 }

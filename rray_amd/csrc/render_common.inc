@@ -85,6 +85,18 @@ __device__ __forceinline__ Px0 level0_px(const LevelArgs& A, int64_t i, int wave
                                          int64_t tile = -1) {
     Px0 r;
     if (A.rays0) {
+#ifdef RR_LISTED
+        // An ordered ray batch (the rr::listed kernels, rr_*_at_device_ordered): slot t works on ray list[t], a
+        // permutation of the batch; ls is the ray's own index, so its jitter identity is sample ls and its result
+        // lands in slot ls.  Slots past the launch's events (i >= A.n: the last wave) hold no ray (ok) and read nothing.
+        if (A.list) {
+            const bool in = i < A.n;
+            if (ok) *ok = in;
+            r.ls = in ? A.list[A.base + i] : 0u;
+            r.px = r.py = r.lrow = 0u;
+            return r;
+        }
+#endif
         r.ls = (uint32_t)(A.base + i);
         r.px = r.py = r.lrow = 0u;
         return r;
@@ -236,7 +248,11 @@ __device__ __forceinline__ Ray event_ray(const LevelArgs& A, int64_t i, const Px
         return {mk(e.o[0], e.o[1], e.o[2]), mk(e.d[0], e.d[1], e.d[2])};
     }
     if (A.rays0) {
+#ifdef RR_LISTED  // an ordered ray batch reads ray q.ls = list[base + i]: a 48-byte gather per lane
+        const double* p = A.list ? A.rays0 + 6 * (int64_t)q.ls : A.rays0 + 6 * (A.base + i);
+#else
         const double* p = A.rays0 + 6 * (A.base + i);
+#endif
         return {mk(p[0], p[1], p[2]), mk(p[3], p[4], p[5])};
     }
     s0 = (uint64_t)q.py * (uint64_t)A.hs + q.px;

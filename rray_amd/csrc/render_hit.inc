@@ -121,6 +121,9 @@ template <int G, bool LC>
 void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
     const dim3 grid(blocks_for(A.n)), block(256);
     const size_t lds = cull_lds(S);
+#ifdef RR_LISTED  // ordered ray batches only (launch_hit_ordered refuses anything else): the one !CAM instantiation
+    hipLaunchKernelGGL((hit_kernel<G, LC, false, true>), grid, block, lds, st, S, A, O);
+#else
 #ifdef RR_VIEWS  // camera samples only (launch_hit_views refuses a ray batch): the CAM instantiations
     if (O.albedo && S.complex_patterns) {
 #else
@@ -132,4 +135,5 @@ void launch_hit_t(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStr
     } else {
         hipLaunchKernelGGL((hit_kernel<G, LC, true, false, false>), grid, block, lds, st, S, A, O);
     }
+#endif
 }

@@ -3,8 +3,12 @@
 //                       (rr_camera_rays_device), by render_common.inc's camera_ray: the frames' own arithmetic
 //   hit_records_kernel  one pass of hit_kernel's ray-batch planes (HitOut.rec_i / rec_d) -> rr_hit records in the
 //                       caller's buffer (rr_hit_at_device)
+//   hit_records_ordered_kernel  the same with a scattered destination: the record of pass slot j goes to ray
+//                       perm[j]'s place (rr_hit_at_device_ordered)
+//   render_order.inc    the coherent order of a ray batch: bounds, keys and a stable radix sort (rr_ray_order_device)
 // Neither reads the scene.  The queries' walks are the existing kernels' (hit_kernel's ray-batch instantiation, the
 // colour families with A.rays0, shadow_query_kernel), launched on the caller's buffers as they are.
+#include <algorithm>
 #include <cstdlib>
 
 #include "device_core.inc"
@@ -46,14 +50,21 @@ constexpr int RR_REC_ROW = RR_REC_TILE + 1;
 static_assert(RR_REC_WORDS * 8 == 192, "rr_hit is 24 words of 8 bytes (rray.h)");
 static_assert(RR_REC_WORDS % 4 == 0 && (RR_REC_TILE * RR_REC_WORDS) % (int)RR_BLOCK == 0, "whole block iterations");
 
-__global__ void __launch_bounds__(256) hit_records_kernel(const int32_t* __restrict__ rec_i,
-                                                          const double* __restrict__ rec_d, int64_t stride, int64_t n,
-                                                          unsigned long long* __restrict__ out) {
+// ORD: record r of the tile goes to out + RR_REC_WORDS * perm[first + r] (whole records still: 24 consecutive words
+// each, so a wave's store covers whole 64-byte runs of 2 to 3 records), else to out + RR_REC_WORDS * (first + r).
+template <bool ORD>
+__device__ __forceinline__ void hit_records_body(const int32_t* __restrict__ rec_i, const double* __restrict__ rec_d,
+                                                 int64_t stride, int64_t n, const uint32_t* __restrict__ perm,
+                                                 unsigned long long* __restrict__ out) {
     __shared__ unsigned long long tile[RR_REC_WORDS * RR_REC_ROW];
+    __shared__ uint32_t dest[ORD ? RR_REC_TILE : 1];
     const int64_t first = (int64_t)blockIdx.x * RR_REC_TILE;
     const int64_t left = n - first;
     const int m = left < RR_REC_TILE ? (int)left : RR_REC_TILE;  // records of this tile (>= 1: the grid is ceil)
     const int r = (int)(threadIdx.x & 63u), w4 = (int)(threadIdx.x >> 6);
+    if constexpr (ORD) {
+        if (w4 == 0 && r < m) dest[r] = perm[first + r];
+    }
 #pragma unroll
     for (int it = 0; it < RR_REC_WORDS / 4; ++it) {  // four planes per step, one per wave
         const int f = it * 4 + w4;
@@ -76,9 +87,30 @@ __global__ void __launch_bounds__(256) hit_records_kernel(const int32_t* __restr
     for (int it = 0; it < RR_REC_TILE * RR_REC_WORDS / (int)RR_BLOCK; ++it) {
         const int w = it * (int)RR_BLOCK + (int)threadIdx.x;
         const int rec = w / RR_REC_WORDS, f = w - rec * RR_REC_WORDS;
-        if (w < words) o[w] = tile[f * RR_REC_ROW + rec];
+        if (w < words) {
+            if constexpr (ORD)
+                out[(int64_t)dest[rec] * RR_REC_WORDS + f] = tile[f * RR_REC_ROW + rec];
+            else
+                o[w] = tile[f * RR_REC_ROW + rec];
+        }
     }
 }
+
+__global__ void __launch_bounds__(256) hit_records_kernel(const int32_t* __restrict__ rec_i,
+                                                          const double* __restrict__ rec_d, int64_t stride, int64_t n,
+                                                          unsigned long long* __restrict__ out) {
+    hit_records_body<false>(rec_i, rec_d, stride, n, nullptr, out);
+}
+
+// perm: the pass's entries of the order (perm[j]: the ray of pass slot j), each < the batch's n — not checked
+__global__ void __launch_bounds__(256) hit_records_ordered_kernel(const int32_t* __restrict__ rec_i,
+                                                                  const double* __restrict__ rec_d, int64_t stride,
+                                                                  int64_t n, const uint32_t* __restrict__ perm,
+                                                                  unsigned long long* __restrict__ out) {
+    hit_records_body<true>(rec_i, rec_d, stride, n, perm, out);
+}
+
+#include "render_order.inc"
 
 hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
@@ -95,6 +127,24 @@ hipError_t launch_hit_records(const HitOut& O, int64_t n, void* out, hipStream_t
     const unsigned grid = (unsigned)((n + RR_REC_TILE - 1) / RR_REC_TILE);
     hipLaunchKernelGGL(hit_records_kernel, dim3(grid), dim3(RR_BLOCK), 0, st, O.rec_i, O.rec_d, O.stride, n,
                        static_cast<unsigned long long*>(out));
+    return hipGetLastError();
+}
+
+hipError_t launch_hit_records_ordered(const HitOut& O, int64_t n, const uint32_t* perm, void* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (!O.rec_i || !O.rec_d || !out || !perm || O.stride < n || n > ((int64_t)1 << 24)) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((n + RR_REC_TILE - 1) / RR_REC_TILE);
+    hipLaunchKernelGGL(hit_records_ordered_kernel, dim3(grid), dim3(RR_BLOCK), 0, st, O.rec_i, O.rec_d, O.stride, n, perm,
+                       static_cast<unsigned long long*>(out));
+    return hipGetLastError();
+}
+
+// one pass of an ordered ray batch through the first-hit kernel's listed instantiation (render_hit.inc under RR_LISTED)
+hipError_t launch_hit_ordered(const DevScene& S, const LevelArgs& A, const HitOut& O, hipStream_t st) {
+    if (A.n <= 0) return hipSuccess;
+    if (!A.rays0 || !A.list || A.n_dev || A.level != 0 || A.base != 0 || !O.rec_i || !O.rec_d || O.stride < A.n)
+        return hipErrorInvalidValue;
+    dispatch_glc(S, [&](auto g, auto lc) { listed::launch_hit_t<g(), lc()>(S, A, O, st); });
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // unit_hit.hip — the first-hit kernels (render_hit.inc hit_kernel: rr_hit_at, rr_render_aov, rr_render_views_aov) of
 // one (G, LC, level-0 source) variant: unit_select.inc.  Objects render[_views]_hit_g<G>_<lds|gl>.  The views variants
-// hold the camera kernels only and carry no cached bundles; there is no listed-pixel first-hit query.
+// hold the camera kernels only and carry no cached bundles; there is no listed-pixel first-hit query (the ordered ray
+// batches' first-hit kernel, the one listed instantiation, is built in the listed level units: unit_levels.hip).
 #include <cstdlib>
 
 #include "device_core.inc"

@@ -579,6 +579,67 @@ class Renderer:
         check(lib().rr_is_shadowed_device(self.h, n, *p))
 
 
+    # ---- ordered ray batches (rray.h RR_HAS_RAY_ORDER) ----
+    def ray_order_device(self, n, d_rays, d_perm, stream=None):
+        """rr_ray_order_device: the coherent order of the n rays at d_rays into d_perm (int: a device pointer to n
+        uint32): d_perm[j] is the ray at position j, argsort(ray_order_keys(rays), kind="stable").  No scene needed.
+        With torch: perm = torch.empty(n, dtype=torch.int32, device=dev) (the bits are unsigned)."""
+        p = [C.c_void_p(x) if x else None for x in (d_rays, d_perm, stream)]
+        check(lib().rr_ray_order_device(self.h, n, *p))
+
+    def color_at_device_ordered(self, n, d_rays, d_rgb, d_perm=None, remaining=5, seed=0, jitter_mode=0, stream=None):
+        """rr_color_at_device_ordered: color_at_device's d_rgb bit for bit, with the waves walking the batch in the
+        order d_perm (None: the library orders the batch itself first, on the same stream).  A d_perm of the caller's
+        must be a permutation of 0..n-1; it is not checked."""
+        p = [C.c_void_p(x) if x else None for x in (d_rays, d_perm)]
+        q = [C.c_void_p(x) if x else None for x in (d_rgb, stream)]
+        check(lib().rr_color_at_device_ordered(self.h, n, *p, remaining, seed, jitter_mode, *q))
+
+    def hit_at_device_ordered(self, n, d_rays, d_hits, d_perm=None, stream=None):
+        """rr_hit_at_device_ordered: hit_at_device's records bit for bit (record i is ray i's), walked in the order
+        d_perm (None: the library's own)."""
+        p = [C.c_void_p(x) if x else None for x in (d_rays, d_perm, d_hits, stream)]
+        check(lib().rr_hit_at_device_ordered(self.h, n, *p))
+
+
+def _spread(q, bits, step):
+    out = np.zeros(q.shape, np.uint32)
+    for k in range(bits):
+        out |= ((q >> np.uint32(k)) & np.uint32(1)) << np.uint32(step * k)
+    return out
+
+
+def ray_order_keys(rays):
+    """The sort key of rr_ray_order_device in numpy (rray.h RR_HAS_RAY_ORDER), the kernels' definition and their
+    tests' reference: rays (n, 6) f64 (origin, direction) -> (n,) uint32, morton3(qx, qy, qz) << 14 | morton2(qu, qv)
+    with the x and u bits lowest.  (u, v): the octahedral map of the direction, in f64 in this order: s = (|dx| + |dy|)
+    + |dz|, px = dx / s, py = dy / s; for dz < 0, u = (1 - |py|) * copysign(1, px), v = (1 - |px|) * copysign(1, py),
+    else u = px, v = py.  A ray is valid iff its six components, u and v are finite; every other ray has the key
+    0xFFFFFFFF.  lo / hi of ox, oy, oz, u, v are taken over the valid rays; q = clamp(floor((c - lo) / (hi - lo) * 2^b),
+    0, 2^b - 1) with b = 6 (origin) or 7 (direction), and 0 where the quotient is not finite (hi == lo)."""
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    keys = np.full(len(r), 0xFFFFFFFF, np.uint32)
+    with np.errstate(all="ignore"):
+        dx, dy, dz = r[:, 3], r[:, 4], r[:, 5]
+        s = (np.abs(dx) + np.abs(dy)) + np.abs(dz)
+        px, py = dx / s, dy / s
+        u = np.where(dz < 0.0, (1.0 - np.abs(py)) * np.copysign(1.0, px), px)
+        v = np.where(dz < 0.0, (1.0 - np.abs(px)) * np.copysign(1.0, py), py)
+        valid = np.isfinite(r).all(axis=1) & np.isfinite(u) & np.isfinite(v)
+        if not valid.any():
+            return keys
+        q = []
+        for c, bits in ((r[:, 0], 6), (r[:, 1], 6), (r[:, 2], 6), (u, 7), (v, 7)):
+            lo, hi = c[valid].min(), c[valid].max()
+            t = (c[valid] - lo) / (hi - lo)
+            f = np.clip(np.floor(t * float(1 << bits)), 0.0, float((1 << bits) - 1))
+            q.append(np.where(np.isfinite(t), f, 0.0).astype(np.uint32))
+    m3 = _spread(q[0], 6, 3) | (_spread(q[1], 6, 3) << np.uint32(1)) | (_spread(q[2], 6, 3) << np.uint32(2))
+    m2 = _spread(q[3], 7, 2) | (_spread(q[4], 7, 2) << np.uint32(1))
+    keys[valid] = (m3 << np.uint32(14)) | m2
+    return keys
+
+
 def adaptive_mask(frame, threshold):
     """The adaptive frames' criterion in numpy (rray.h rr_render_adaptive, rule 2): pixel p of frame (H, W, 3) is
     refined iff some q of its 3x3 neighbourhood, clipped to the frame (q = p included), has
