@@ -481,6 +481,64 @@ int rr_color_at_device_ordered(rr_ctx* ctx, int64_t n, const void* d_rays, const
 int rr_hit_at_device_ordered(rr_ctx* ctx, int64_t n, const void* d_rays, const void* d_perm, void* d_hits,
                              void* hip_stream);
 
+/* ---- lens frames: depth of field and jittered samples per pixel (additive to ABI 11; test RR_HAS_LENS) ----
+ * A frame with S rays per pixel through a finite aperture, with optional sub-pixel jitter: depth of field, and S
+ * decorrelated area-light samples per pixel, in one call with an exact, repeatable definition.  `cam` is the camera at
+ * OUTPUT size W x H (cam->hsize x cam->vsize); opts->aa must be 1 (the S samples take aa's place).  Pixel p = py * W +
+ * px; sample s of pixel p is ray i = p * S + s of the frame's batch (W * H * S < 2^32).
+ * The rays (rr_lens_rays_device writes those of pixels [first_pixel, first_pixel + n_pixels): rr_camera_rays_device's
+ * layout, six doubles per ray, ray i at d_rays + 6 * (i - first_pixel * S); no scene needed; ordered on the stream, not
+ * synchronised).  Plain f64 in exactly this order, no contraction; rray_amd.lens_rays is the same in numpy:
+ *   base = jitter_base(lens.seed, i, 0) (path 0 is free: shading paths start at 1); u(k) = jitter_value(base, 0, k >> 1,
+ *     k & 1) = lowbias32(base ^ k) * 2^-32 in [0, 1)
+ *   jx, jy = pixel_jitter ? (u(0), u(1)) : (0.5, 0.5)
+ *   wx = half_width - ((double)px + jx) * pixel_size;  wy = half_height - ((double)py + jy) * pixel_size
+ *   X(x, y, z)[r] = ((M[4r] * x + M[4r+1] * y) + M[4r+2] * z) + M[4r+3] * 1.0, M the camera's inverse as the frames
+ *     compute it (rr_camera_inverse returns those 16 doubles; host only)
+ *   aperture == 0 (a pinhole): o = X(0, 0, 0), f = X(wx, wy, -1)
+ *   aperture > 0 (a thin lens): for a = 0..7: A = 2 * u(2 + 2a) - 1, B = 2 * u(3 + 2a) - 1; the first pair with
+ *     A * A + B * B <= 1 is taken, A = B = 0 if there is none (probability (1 - pi/4)^8, about 4.5e-6 per ray; the
+ *     rejection loop needs no sin / cos); o = X(aperture * A, aperture * B, 0.0), f = X(wx * fd, wy * fd, -fd) with
+ *     fd = focal_distance: every sample of a pixel without jitter passes the same point of the plane in focus
+ *   d = f - o, mag = sqrt((dx * dx + dy * dy) + dz * dz), direction d / mag by IEEE division
+ * With samples == 1, no jitter and no aperture the rays are rr_camera_rays_device's bit for bit.  A camera whose inverse
+ * is not affine (last row other than 0, 0, 0, 1) is refused with RR_E_NONAFFINE.
+ * The frame: avg[p][c] = (((c_0 + c_1) + ...) + c_{S-1}) / (double)S per channel, c_s what rr_color_at_device writes
+ * for ray p * S + s of the whole frame's batch with remaining = opts->max_depth, opts->seed and opts->jitter_mode (the
+ * area-light jitter identity of sample p * S + s, path 1).  out_avg / d_avg: H x W x 3 doubles.
+ * The frame runs in passes of whole pixels; every pass but the last holds a multiple of 64 pixels, so a pass starts at
+ * a ray index that is a multiple of 64 and its waves are the one-shot batch's.  Default pass: the largest such count
+ * with at most 2^22 rays (at least 64 pixels); RRAY_LENS_PASS=<pixels> overrides it (rounded up to a multiple of 64, read
+ * at context creation).  Context-owned scratch holds one pass's rays and colours (48 + 24 bytes per ray), grows on
+ * demand and is freed with the context (RR_E_HIP when it cannot be allocated).
+ * rr_last_stats / stats after a frame: samples == W * H * S; rays, shadow_rays, shade_events, n1n2_scans and nan_rays
+ * are what one rr_color_at_device over the whole batch reports; kernel_ms is one event pair around the frame (0 with
+ * RR_NO_FRAME_TIMING).  Frame state is left alone, as by the ray entries.
+ * rr_render_lens: host buffer, blocking, RR_E_NAN after writing when nan_rays > 0.  rr_render_lens_device: a device
+ * buffer, enqueued on `hip_stream` (NULL: ctx stream) and NOT synchronised, stream claim and device guard of the other
+ * _device entries; NaN rays are reported through nan_rays.
+ * RR_E_ARG: a null pointer, samples outside 1..RR_MAX_LENS_SAMPLES, aperture negative or not finite, focal_distance
+ * not finite and positive while aperture > 0, aa != 1, part != 0, nparts != 1, a row band, any flag but
+ * RR_NO_FRAME_TIMING, a first_pixel / n_pixels window outside the frame, a multi-device or virtual context, no scene
+ * uploaded (frames only).  RR_E_LIMIT: W * H * S >= 2^32, max_depth outside 0..RR_MAX_DEPTH.  n_pixels == 0: RR_OK,
+ * nothing enqueued. */
+#define RR_HAS_LENS 1
+#define RR_MAX_LENS_SAMPLES 4096
+typedef struct {
+    int32_t samples;        /* S: rays per pixel, 1..RR_MAX_LENS_SAMPLES */
+    int32_t pixel_jitter;   /* 0: every sample through the pixel centre (camera.rs's +0.5); 1: uniform in the pixel */
+    double aperture;        /* lens radius in camera space; 0: a pinhole.  Finite, >= 0 */
+    double focal_distance;  /* camera-space distance of the plane in focus (z = -focal_distance); finite, > 0; ignored when aperture == 0 */
+    uint64_t seed;          /* seed of the pixel / lens samples (opts->seed stays the area lights') */
+} rr_lens;
+int rr_camera_inverse(const rr_camera* cam, double inv[16]);
+int rr_lens_rays_device(rr_ctx* ctx, const rr_camera* cam, const rr_lens* lens, int64_t first_pixel, int64_t n_pixels,
+                        void* d_rays, void* hip_stream);
+int rr_render_lens(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_lens* lens, double* out_avg,
+                   rr_stats* stats);
+int rr_render_lens_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_lens* lens,
+                          void* d_avg, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

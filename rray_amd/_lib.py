@@ -83,7 +83,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_render_adaptive_device", "rr_resident_launch", "rr_render_views", "rr_render_views_device",
            "rr_render_views_aov", "rr_render_views_aov_device", "rr_camera_rays_device", "rr_color_at_device",
            "rr_hit_at_device", "rr_is_shadowed_device", "rr_ray_order_device", "rr_color_at_device_ordered",
-           "rr_hit_at_device_ordered"]
+           "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
+           "rr_render_lens_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -97,6 +98,15 @@ class Hit(C.Structure):
                 ("point", C.c_double * 3), ("eyev", C.c_double * 3), ("normalv", C.c_double * 3),
                 ("over_point", C.c_double * 3), ("under_point", C.c_double * 3), ("reflectv", C.c_double * 3),
                 ("n1", C.c_double), ("n2", C.c_double)]
+
+
+RR_MAX_LENS_SAMPLES = 4096
+
+
+class LensDesc(C.Structure):
+    """rr_lens (RR_HAS_LENS): samples per pixel, sub-pixel jitter, thin-lens aperture and focus, the samples' seed."""
+    _fields_ = [("samples", C.c_int32), ("pixel_jitter", C.c_int32), ("aperture", C.c_double),
+                ("focal_distance", C.c_double), ("seed", C.c_uint64)]
 
 
 def hit_dtype():
@@ -195,6 +205,14 @@ def lib():
     L.rr_color_at_device_ordered.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
                                              C.c_int32, C.c_void_p, C.c_void_p]
     L.rr_hit_at_device_ordered.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # lens frames (RR_HAS_LENS)
+    L.rr_camera_inverse.argtypes = [C.POINTER(Camera), _D]
+    L.rr_lens_rays_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(LensDesc), C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p]
+    L.rr_render_lens.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(LensDesc), _D,
+                                 C.POINTER(Stats)]
+    L.rr_render_lens_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(LensDesc),
+                                        C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -87,6 +87,10 @@ struct rr_ctx {
     // ordered ray batches (rr_ray_order_device, rr_*_at_device_ordered): the sort's scratch (rr::ray_order_scratch_bytes)
     // and the order of a call that brings none (d_perm == NULL); grow on demand, freed with the context
     DBuf order_scratch, order_perm;
+    // lens frames (rr_render_lens_device): one pass's rays (48 bytes each) and colours (24), grown on demand; the pass
+    // size RRAY_LENS_PASS asks for in pixels (0: rr::plan_lens_passes' default), read at context creation
+    DBuf lens_rays, lens_rgb;
+    int64_t lens_pass = 0;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -694,17 +698,21 @@ int average_pass(rr_ctx* c, const rr::FramePlan& plan, const FrameOut& o, int64_
 // Runs the wavefront levels for `total` level-0 events; level-0 rays come from the camera or from ctx->rays0
 // (color_at).  Results (color_at values) land in `out` (3 doubles per event), or averaged in `avg`.  facts: the
 // call's frame_facts for this max_depth.  frame_plan.hpp decides what runs; the steps below launch it.
+// base0: the index of the run's first event (a multiple of 64 and rays0 only: a pass of a lens frame, whose events are
+// the frame's base0 .. base0 + total — sample identity, ray and output slot — through pointers the caller biased by
+// -base0 entries).
 int run_levels(rr_ctx* c, const FrameFacts& facts, const rr::LevelArgs& base_args, int64_t total, int max_depth,
                double* out, hipStream_t st, void* avg = nullptr, int32_t avg_f32 = 0, int32_t aa_wave = 0,
-               const AaPasses* aap = nullptr) {
+               const AaPasses* aap = nullptr, int64_t base0 = 0) {
     const FrameOut o{out, avg, avg_f32, aa_wave, aap};
     const rr::FramePlan plan = plan_run(c, facts, base_args, total, max_depth, o);
     if (plan.err != RR_OK) return fail(plan.err, plan.msg);
     int rc = grow_workspace(c, plan);
     if (rc == RR_OK && plan.order.ok) rc = refresh_order(c, base_args, plan, !facts.sw.no_tile_guess, st);
     if (rc != RR_OK) return rc;
-    for (int64_t base = 0; base < total; base += plan.B) {
-        const int64_t nb = std::min(plan.B, total - base);
+    if (base0 != 0 && (!base_args.rays0 || base0 % 64 != 0 || aap)) return fail(RR_E_ARG, "internal: a starting base needs explicit rays and whole waves");
+    for (int64_t off = 0; off < total; off += plan.B) {
+        const int64_t base = base0 + off, nb = std::min(plan.B, total - off);
         rr::LevelPlan short_batch;
         if (nb != plan.B) short_batch = rr::plan_levels(nb, plan.k, plan.plan_depth, plan.ext, plan.fused);
         const rr::LevelPlan& p = nb != plan.B ? short_batch : plan.P;
@@ -721,7 +729,7 @@ int run_levels(rr_ctx* c, const FrameFacts& facts, const rr::LevelArgs& base_arg
             if (plan.order.ok && d == 0 && (rc = age_order(c, plan, st)) != RR_OK) return rc;
         }
         if (plan.family == rr::Family::Unfused) rc = combine_levels(c, base_args, plan, p, base, o, st);
-        if (rc == RR_OK && plan.passes) rc = average_pass(c, plan, o, base_args.hs, base, nb, st);
+        if (rc == RR_OK && plan.passes) rc = average_pass(c, plan, o, base_args.hs, off, nb, st);
         if (rc != RR_OK) return rc;
     }
     if (plan.passes) {  // the caller's stream continues after the last pass's average
@@ -836,6 +844,7 @@ int rr_create(int device, rr_ctx** out) {
     rr_ctx* c = new rr_ctx();
     c->device = device;
     if (const char* b = std::getenv("RRAY_BATCH")) c->batch = std::max<int64_t>(1024, std::atoll(b));
+    if (const char* b = std::getenv("RRAY_LENS_PASS")) c->lens_pass = std::max<int64_t>(0, std::atoll(b));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) c->queue_budget = free_b / 2;
     if (const char* q = std::getenv("RRAY_QUEUE_BUDGET_MB")) c->queue_budget = (size_t)std::max(1ll, std::atoll(q)) << 20;
@@ -909,7 +918,7 @@ void rr_destroy(rr_ctx* c) {
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
-                    &c->shadow_sink, &c->order_scratch, &c->order_perm})
+                    &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2180,6 +2189,162 @@ int rr_is_shadowed_device(rr_ctx* c, int64_t n, const void* d_points, const void
                                    n, static_cast<int32_t*>(d_out), c->shadow_sink.as<unsigned long long>(), st));
     HIPCHK(claim.release());
     return RR_OK;
+}
+
+// ---- lens frames (render_lens.inc) ----
+// S rays per pixel from lens_rays_kernel, traced by the colour families' rays0 path a pass of whole pixels at a time and
+// summed per pixel by lens_resolve_kernel.  The isolation rule of the ray queries holds: counters in buffer 2, no frame
+// state touched.
+int rr_camera_inverse(const rr_camera* cam, double inv[16]) {
+    if (!cam || !inv) return fail(RR_E_ARG, "rr_camera_inverse: null argument");
+    const rr::DevCamera d = dev_camera(cam);
+    for (int i = 0; i < 16; ++i) inv[i] = d.inv[i];
+    return RR_OK;
+}
+
+// what the lens entries refuse of the camera and the lens alike; fills the kernel's argument
+static int lens_check(const rr_camera* cam, const rr_lens* lens, rr::DevLens* L) {
+    if (!cam || !lens) return fail(RR_E_ARG, "lens frames: null camera / lens");
+    if (lens->samples < 1 || lens->samples > RR_MAX_LENS_SAMPLES)
+        return fail(RR_E_ARG, "lens samples must be in 1.." + std::to_string(RR_MAX_LENS_SAMPLES));
+    if (!(std::isfinite(lens->aperture) && lens->aperture >= 0.0)) return fail(RR_E_ARG, "the aperture must be finite and >= 0");
+    if (lens->aperture > 0.0 && !(std::isfinite(lens->focal_distance) && lens->focal_distance > 0.0))
+        return fail(RR_E_ARG, "the focal distance of a thin lens must be finite and > 0");
+    if (cam->hsize < 1 || cam->vsize < 1) return fail(RR_E_ARG, "camera sizes must be >= 1");
+    if (cam->hsize >= ((int64_t)1 << 32) || cam->vsize >= ((int64_t)1 << 32) ||
+        cam->hsize * cam->vsize >= ((int64_t)1 << 32) || cam->hsize * cam->vsize * lens->samples >= ((int64_t)1 << 32))
+        return fail(RR_E_LIMIT, "a lens frame's rays (W * H * samples) must number fewer than 2^32");
+    rr::LevelArgs A{};
+    set_camera(A, cam);  // the frames' DevCamera and affine flag
+    if (!A.cam_affine) return fail(RR_E_NONAFFINE, "lens frames need a camera whose inverse is affine (last row 0, 0, 0, 1)");
+    for (int i = 0; i < 12; ++i) L->inv[i] = A.cam.inv[i];
+    L->half_width = A.cam.half_width;
+    L->half_height = A.cam.half_height;
+    L->pixel_size = A.cam.pixel_size;
+    L->aperture = lens->aperture;
+    L->focal_distance = lens->aperture > 0.0 ? lens->focal_distance : 1.0;
+    L->seed = lens->seed;
+    L->samples = (uint32_t)lens->samples;
+    L->width = (uint32_t)cam->hsize;
+    L->pixel_jitter = lens->pixel_jitter ? 1 : 0;
+    L->pad = 0;
+    return RR_OK;
+}
+
+int rr_lens_rays_device(rr_ctx* c, const rr_camera* cam, const rr_lens* lens, int64_t first_pixel, int64_t n_pixels,
+                        void* d_rays, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    if (!c || !d_rays) return fail(RR_E_ARG, "rr_lens_rays_device: null argument");
+    if (c->group) return fail(RR_E_ARG, "lens frames need a single-device context (no multi-device or virtual context)");
+    rr::DevLens L{};
+    int rc = lens_check(cam, lens, &L);
+    if (rc != RR_OK) return rc;
+    if (first_pixel < 0 || n_pixels < 0 || first_pixel > cam->hsize * cam->vsize ||
+        n_pixels > cam->hsize * cam->vsize - first_pixel)
+        return fail(RR_E_ARG, "the pixel window [first_pixel, first_pixel + n_pixels) must lie inside the frame");
+    if (n_pixels == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    HIPCHK(rr::launch_lens_rays(L, first_pixel * L.samples, n_pixels * L.samples, static_cast<double*>(d_rays), st));
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+// what both frame entries refuse before they look at the context
+static int lens_frame_check(const rr_camera* cam, const rr_render_opts* o, const rr_lens* lens, const void* avg,
+                            rr::DevLens* L) {
+    if (!cam || !o || !lens || !avg) return fail(RR_E_ARG, "rr_render_lens: null argument");
+    if (o->aa != 1) return fail(RR_E_ARG, "lens frames take opts->aa == 1: the lens samples take aa's place");
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "lens frames are whole frames: part 0 of 1, no band");
+    if (o->flags & ~RR_NO_FRAME_TIMING) return fail(RR_E_ARG, "lens frames take no flag but RR_NO_FRAME_TIMING");
+    if (o->max_depth < 0 || o->max_depth > RR_MAX_DEPTH) return fail(RR_E_LIMIT, "max_depth out of range");
+    return lens_check(cam, lens, L);
+}
+
+int rr_render_lens_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_lens* lens, void* d_avg,
+                          void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevLens L{};
+    int rc = lens_frame_check(cam, o, lens, d_avg, &L);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "lens frames need a single-device context (no multi-device or virtual context)");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    const int64_t S = lens->samples, n_pixels = cam->hsize * cam->vsize;
+    const rr::LensPassPlan plan = rr::plan_lens_passes(n_pixels, lens->samples, c->lens_pass);
+    const int64_t pass_rays = std::min(plan.pixels, n_pixels) * S;
+    const FrameFacts facts = frame_facts(c, o->max_depth);
+    HIPCHK(hipSetDevice(c->device));
+    // one pass's rays and colours (grown on demand, as rr_hit_at_device's planes)
+    HIPCHK(c->lens_rays.ensure((size_t)pass_rays * 6 * sizeof(double)));
+    HIPCHK(c->lens_rgb.ensure((size_t)pass_rays * 3 * sizeof(double)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = !(o->flags & RR_NO_FRAME_TIMING);
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e0, st));
+    const int saved_epoch = c->epoch;
+    c->epoch = 2;  // the query buffer (frame buffers keep their state), zeroed once per frame
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));
+    rr::LevelArgs A{};  // rr_color_at_device's level 0: sample i's jitter identity is (i, path 1)
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.seed = o->seed;
+    A.jitter_mode = o->jitter_mode;
+    double* const rays = c->lens_rays.as<double>();
+    double* const rgb = c->lens_rgb.as<double>();
+    for (int64_t first = 0; first < n_pixels && rc == RR_OK; first += plan.pixels) {
+        const int64_t np = std::min(plan.pixels, n_pixels - first), r0 = first * S;
+        hipError_t e = rr::launch_lens_rays(L, r0, np * S, rays, st);
+        if (e != hipSuccess) {
+            rc = fail(RR_E_HIP, std::string("launch_lens_rays: ") + hipGetErrorString(e));
+            break;
+        }
+        // The pass's events are the frame's r0 .. r0 + np * S: the kernels index the rays, the sample identity and the
+        // output slot by base + lane, so the scratch pointers are biased by -r0 entries and never dereferenced outside
+        // the pass (integer arithmetic: the biased addresses may lie below the allocations).
+        A.rays0 = reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(rays) - (uintptr_t)r0 * 6 * sizeof(double));
+        double* out = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(rgb) - (uintptr_t)r0 * 3 * sizeof(double));
+        rc = run_levels(c, facts, A, np * S, o->max_depth, out, st, nullptr, 0, 0, nullptr, r0);
+        if (rc != RR_OK) break;
+        e = rr::launch_lens_resolve(rgb, lens->samples, np, static_cast<double*>(d_avg) + 3 * first, st);
+        if (e != hipSuccess) rc = fail(RR_E_HIP, std::string("launch_lens_resolve: ") + hipGetErrorString(e));
+    }
+    c->epoch = saved_epoch;
+    if (rc != RR_OK) return rc;
+    if (c->frame_timed) HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n_pixels * S);
+    return RR_OK;
+}
+
+int rr_render_lens(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_lens* lens, double* out_avg,
+                   rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevLens L{};
+    int rc = lens_frame_check(cam, o, lens, out_avg, &L);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "lens frames need a single-device context (no multi-device or virtual context)");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    const size_t img = (size_t)(cam->hsize * cam->vsize) * 3 * sizeof(double);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->qout.ensure(img));
+    rc = rr_render_lens_device(c, cam, o, lens, c->qout.p, nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out_avg, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
 }
 
 }  // extern "C"

@@ -6,6 +6,10 @@
 // <PREFIX>_albedo.png, the camera rays' first-hit planes (rr_render_aov) at the supersampled size.
 // --adaptive <THRESHOLD> renders the PNG through rr_render_adaptive: the aa 1 frame, supersampled (-a) only where a
 // pixel differs from a neighbour by more than THRESHOLD in some channel (one device).
+// --samples <S>, --aperture <A>, --focus <F> and --pixel-jitter render the PNG through rr_render_lens: S rays per pixel
+// (default 1) through a thin lens of radius A (default 0: a pinhole) focused at camera-space distance F (default 1), each
+// through the pixel centre or, with --pixel-jitter, a point uniform in the pixel (one device; not with -a, --adaptive or
+// --aov).
 // No CPU fallback.
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +33,10 @@ static int usage(const char* msg) {
                  "  -a, --aa <AA>          Anti-aliasing level (default 1) (max 5) [default: 1]\n"
                  "      --aov <PREFIX>     Also write <PREFIX>_normal.png and <PREFIX>_albedo.png (first-hit planes)\n"
                  "      --adaptive <THRESHOLD>  Supersample only pixels that differ from a neighbour by more than THRESHOLD\n"
+                 "      --samples <S>      Lens frame: S rays per pixel (1..4096) [default: 1]\n"
+                 "      --aperture <A>     Lens frame: lens radius in camera space, 0 is a pinhole [default: 0]\n"
+                 "      --focus <F>        Lens frame: camera-space distance of the plane in focus [default: 1]\n"
+                 "      --pixel-jitter     Lens frame: each sample through a point uniform in its pixel\n"
                  "  -h, --help             Print help\n  -V, --version          Print version\n");
     return 2;
 }
@@ -126,11 +134,60 @@ static int render_adaptive(const std::string& scene, long long width, long long 
     return rc;
 }
 
+// --samples / --aperture / --focus / --pixel-jitter: the colour image through rr_render_lens (camera.rs:113's depth 5
+// and seed 0, as the plain path)
+static int render_lens(const std::string& scene, long long width, long long height, int device, const rr_lens& lens,
+                       const std::string& output) {
+    std::ifstream f(scene, std::ios::binary);
+    if (!f) {  // scene_builder_yaml.rs:434 panics "File does not exist"
+        std::fprintf(stderr, "rray: File does not exist (code %d)\n", RR_E_IO);
+        return RR_E_IO;
+    }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    rr_scene* S = nullptr;
+    rr_camera cam;
+    int rc = rr_scene_from_yaml(ss.str().c_str(), nullptr, width, height, 1, &S, &cam);
+    rr_ctx* ctx = nullptr;
+    if (rc == RR_OK) rc = rr_create(device, &ctx);
+    if (rc == RR_OK) rc = rr_scene_upload(ctx, rr_scene_desc_of(S));
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<double> avg(n * 3);
+    if (rc == RR_OK) {
+        rr_render_opts o{};
+        o.aa = 1;
+        o.max_depth = 5;
+        o.nparts = 1;
+        o.block_rows = 8;
+        rc = rr_render_lens(ctx, &cam, &o, &lens, avg.data(), nullptr);
+    }
+    if (rc == RR_OK) {
+        std::vector<uint8_t> rgba(n * 4);
+        rr_quantize(avg.data(), (int64_t)n, rgba.data());
+        rc = rr_write_png(output.c_str(), rgba.data(), width, height);
+        if (rc != RR_OK) std::fprintf(stderr, "rray: cannot write PNG (code %d)\n", rc);
+    } else {
+        std::fprintf(stderr, "rray: lens frame: %s (code %d)\n", rr_last_error(), rc);
+    }
+    rr_destroy(ctx);
+    rr_scene_free(S);
+    return rc;
+}
+
+static bool parse_double(const char* v, double& out) {
+    char* end = nullptr;
+    out = std::strtod(v, &end);
+    return end != v && !*end && std::isfinite(out);
+}
+
 int main(int argc, char** argv) {
     long long width = 800, height = 600, aa = 1;
     std::string scene, output = "output.png", aov;
-    bool adaptive = false;
+    bool adaptive = false, lens_frame = false;
     double threshold = 0.0;
+    rr_lens lens{};
+    lens.samples = 1;
+    lens.focal_distance = 1.0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -159,6 +216,23 @@ int main(int argc, char** argv) {
             threshold = std::strtod(v, &end);
             if (end == v || *end || std::isnan(threshold)) return usage("--adaptive needs a number (the colour threshold)");
             adaptive = true;
+        } else if (a == "--samples") {
+            long long S = 0;
+            if (!parse_usize(val("--samples"), S) || S < 1 || S > RR_MAX_LENS_SAMPLES)
+                return usage("--samples needs a number from 1 to 4096");
+            lens.samples = (int32_t)S;
+            lens_frame = true;
+        } else if (a == "--aperture") {
+            if (!parse_double(val("--aperture"), lens.aperture) || lens.aperture < 0.0)
+                return usage("--aperture needs a number >= 0 (the lens radius)");
+            lens_frame = true;
+        } else if (a == "--focus") {
+            if (!parse_double(val("--focus"), lens.focal_distance) || !(lens.focal_distance > 0.0))
+                return usage("--focus needs a number > 0 (the distance of the plane in focus)");
+            lens_frame = true;
+        } else if (a == "--pixel-jitter") {
+            lens.pixel_jitter = 1;
+            lens_frame = true;
         } else if (a == "-a" || a == "--aa") {
             if (!parse_usize(val("--aa"), aa)) return usage("must be a positive number");  // main.rs:21-27
             if (aa > 5) return usage("value must be less than or equal to 5");
@@ -168,6 +242,8 @@ int main(int argc, char** argv) {
     }
     if (scene.empty()) return usage("the following required arguments were not provided: --scene <SCENE>");
     if (width <= 0 || height <= 0 || aa <= 0) return usage("width, height and aa must be >= 1");
+    if (lens_frame && (aa != 1 || adaptive || !aov.empty()))
+        return usage("--samples, --aperture, --focus and --pixel-jitter cannot be combined with -a other than 1, --adaptive or --aov");
     std::vector<int> devices;
     if (const char* ds = std::getenv("RRAY_DEVICES")) {
         if (std::strcmp(ds, "all") == 0) {
@@ -192,7 +268,10 @@ int main(int argc, char** argv) {
         devices.push_back(std::getenv("RRAY_DEVICE") ? std::atoi(std::getenv("RRAY_DEVICE")) : 0);
     }
     int rc;
-    if (adaptive) {
+    if (lens_frame) {
+        if (devices.size() != 1) return usage("a lens frame renders on one device");
+        if (render_lens(scene, width, height, devices[0], lens, output) != RR_OK) return 1;
+    } else if (adaptive) {
         if (devices.size() != 1) return usage("--adaptive renders on one device");
         if (render_adaptive(scene, width, height, (int)aa, devices[0], threshold, output) != RR_OK) return 1;
     } else {

@@ -198,6 +198,26 @@ inline RayPassPlan plan_ray_passes(int64_t n, int64_t batch) {
     return p;
 }
 
+// The pass split of rr_render_lens_device (lens frames): passes of whole pixels, S rays each.  Every
+// pass but the last holds `pixels` pixels, a multiple of 64, so each pass starts at a ray index that is a multiple of 64
+// and its level-0 waves are the one-shot batch's.  want > 0 (RRAY_LENS_PASS): that many pixels rounded up to a multiple
+// of 64; else the largest multiple of 64 with at most kRayPassMax rays, and at least 64 pixels.  Pass k holds pixels
+// [k * pixels, min(n_pixels, (k + 1) * pixels)).
+struct LensPassPlan {
+    int64_t pixels;  // per pass (the last may be shorter)
+    int64_t passes;
+};
+inline LensPassPlan plan_lens_passes(int64_t n_pixels, int32_t samples, int64_t want) {
+    LensPassPlan p{};
+    if (n_pixels <= 0 || samples < 1) return p;
+    if (want > 0)
+        p.pixels = want > ((int64_t)1 << 40) ? (int64_t)1 << 40 : (want + 63) / 64 * 64;
+    else
+        p.pixels = std::max<int64_t>(64, kRayPassMax / samples / 64 * 64);
+    p.passes = (n_pixels + p.pixels - 1) / p.pixels;
+    return p;
+}
+
 struct FramePlan {
     Family family;
     bool fused, ext;  // segmented queues between the levels; refraction halves beside the pending sums

@@ -363,4 +363,21 @@ hipError_t launch_hit_ordered(const DevScene& S, const LevelArgs& A, const HitOu
 // hit_records_kernel with a scattered destination: the record of pass slot j goes to out + 192 * perm[j], whole
 hipError_t launch_hit_records_ordered(const HitOut& O, int64_t n, const uint32_t* perm, void* out, hipStream_t stream);
 
+// Lens frames (render_lens.inc in render_rays.hip; the definition is rray.h's RR_HAS_LENS block).
+// What lens_rays_kernel reads of the camera and the lens: the affine rows of the frames' camera inverse (api.cpp
+// set_camera), the image plane, the lens and the frame's geometry.  A kernel argument of its own, never part of LevelArgs.
+struct DevLens {
+    double inv[12];  // rows 0..2 of DevCamera.inv (row 3 is 0, 0, 0, 1: host-checked)
+    double half_width, half_height, pixel_size;
+    double aperture, focal_distance;
+    uint64_t seed;
+    uint32_t samples, width;  // S and W; ray i is sample i % S of pixel i / S, pixel p at (p % W, p / W)
+    int32_t pixel_jitter, pad;
+};
+// lens_rays_kernel: the rays [first_ray, first_ray + n) of the frame (first_ray + n <= 2^32), ray first_ray + j at
+// out + 6 * j
+hipError_t launch_lens_rays(const DevLens& L, int64_t first_ray, int64_t n, double* out, hipStream_t stream);
+// lens_resolve_kernel: out[p] = (((c[p*S] + c[p*S + 1]) + ...) + c[p*S + S - 1]) / (double)S per channel, p < n_pixels
+hipError_t launch_lens_resolve(const double* colours, int32_t samples, int64_t n_pixels, double* out, hipStream_t stream);
+
 }  // namespace rr

@@ -601,6 +601,34 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_rays, d_perm, d_hits, stream)]
         check(lib().rr_hit_at_device_ordered(self.h, n, *p))
 
+    # ---- lens frames (rray.h RR_HAS_LENS): depth of field and jittered samples per pixel ----
+    def lens_rays_device(self, cam, lens, d_rays, first_pixel=0, n_pixels=None, stream=None):
+        """rr_lens_rays_device: the rays of pixels [first_pixel, first_pixel + n_pixels) of `cam` under `lens` into
+        d_rays (int: a device pointer to n_pixels * lens.samples * 6 f64), lens_rays(cam, lens, ...) bit for bit.
+        Ordered on `stream` (int or None), not synchronised; no scene needed."""
+        n = cam.hsize * cam.vsize - first_pixel if n_pixels is None else n_pixels
+        d = lens.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_rays, stream)]
+        check(lib().rr_lens_rays_device(self.h, C.byref(cam), C.byref(d), first_pixel, n, *p))
+
+    def render_lens(self, cam, lens, max_depth=5, seed=0, jitter_mode=0):
+        """rr_render_lens: a frame of lens.samples rays per pixel of `cam` (at output size, aa 1) ->
+        dict(avg=(H, W, 3) f64, stats): lens_resolve of color_at_device over lens_rays_device(cam, lens), bit for bit;
+        sample s of pixel p has the area-light jitter identity of sample p * S + s.  stats['samples'] == W * H * S."""
+        o = _lib.RenderOpts(1, max_depth, seed, jitter_mode, 0, 1, 8, 0, 0, 0)
+        d = lens.desc()
+        avg = np.zeros((cam.vsize, cam.hsize, 3), np.float64)
+        st = _lib.Stats()
+        check(lib().rr_render_lens(self.h, C.byref(cam), C.byref(o), C.byref(d), _dp(avg), C.byref(st)))
+        return {"avg": avg, "stats": st.as_dict()}
+
+    def render_lens_device(self, cam, opts, lens, d_avg, stream=None):
+        """rr_render_lens_device: the frame into d_avg (int: a device pointer to H * W * 3 f64), ordered on `stream`
+        (int or None), not synchronised; NaN rays are counted in last_stats()['nan_rays'], never raised."""
+        d = lens.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_avg, stream)]
+        check(lib().rr_render_lens_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
+
 
 def _spread(q, bits, step):
     out = np.zeros(q.shape, np.uint32)
@@ -638,6 +666,117 @@ def ray_order_keys(rays):
     m2 = _spread(q[3], 7, 2) | (_spread(q[4], 7, 2) << np.uint32(1))
     keys[valid] = (m3 << np.uint32(14)) | m2
     return keys
+
+
+class Lens:
+    """rr_lens (rray.h RR_HAS_LENS): `samples` rays per pixel, each through the pixel centre or (pixel_jitter) a point
+    uniform in the pixel, from a point of a lens of radius `aperture` (0: a pinhole) focused at camera-space distance
+    focal_distance; `seed` seeds the pixel / lens samples (the render's own seed stays the area lights')."""
+
+    def __init__(self, samples=1, pixel_jitter=False, aperture=0.0, focal_distance=1.0, seed=0):
+        self.samples, self.pixel_jitter = int(samples), bool(pixel_jitter)
+        self.aperture, self.focal_distance, self.seed = float(aperture), float(focal_distance), int(seed)
+
+    def desc(self):
+        return _lib.LensDesc(self.samples, 1 if self.pixel_jitter else 0, self.aperture, self.focal_distance,
+                             self.seed & 0xFFFFFFFFFFFFFFFF)
+
+    def __repr__(self):
+        return (f"Lens(samples={self.samples}, pixel_jitter={self.pixel_jitter}, aperture={self.aperture}, "
+                f"focal_distance={self.focal_distance}, seed={self.seed})")
+
+
+def _splitmix64(x):
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _lowbias32(x):
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def lens_hash(seed, ray, k):
+    """u(k) of ray `ray` (arrays broadcast) under `seed`: the counter hash of the lens frames, jitter_value(jitter_base(
+    seed, ray, path 0), light 0, k >> 1, k & 1) = lowbias32(base ^ k) * 2^-32 in [0, 1) — the area lights' hash with
+    the path shading never uses."""
+    with np.errstate(over="ignore"):
+        i = np.asarray(ray, np.uint64)
+        base = (_splitmix64(np.uint64(seed & 0xFFFFFFFFFFFFFFFF) ^ _splitmix64(i)) >> np.uint64(32)).astype(np.uint32)
+        return _lowbias32(base ^ np.asarray(k, np.uint32)).astype(np.float64) * (1.0 / 4294967296.0)
+
+
+def camera_inverse(cam):
+    """rr_camera_inverse: the 16 doubles of the camera's inverse as the frames compute it (host only)."""
+    out = np.zeros(16, np.float64)
+    check(lib().rr_camera_inverse(C.byref(cam), _dp(out)))
+    return out
+
+
+def lens_rays(cam, lens, first_pixel=0, n_pixels=None):
+    """The lens frames' rays in numpy (rray.h RR_HAS_LENS), the kernel's definition and its tests' reference: the rays of
+    pixels [first_pixel, first_pixel + n_pixels) of `cam` (at output size) under `lens`, (n_pixels * samples, 6) f64 —
+    origin, direction; sample s of pixel p = py * W + px is ray i = p * S + s.  Plain f64 in this order, with u(k) =
+    lens_hash(lens.seed, i, k) and M = camera_inverse(cam):
+      jx, jy = (u(0), u(1)) with pixel_jitter, else (0.5, 0.5); wx = half_width - (px + jx) * pixel_size, wy likewise
+      X(x, y, z)[r] = ((M[4r] x + M[4r+1] y) + M[4r+2] z) + M[4r+3] * 1.0
+      pinhole (aperture == 0): o = X(0, 0, 0), f = X(wx, wy, -1)
+      thin lens: (A, B) = the first of (2 u(2 + 2a) - 1, 2 u(3 + 2a) - 1), a = 0..7, with A A + B B <= 1, else (0, 0);
+        o = X(aperture A, aperture B, 0), f = X(wx fd, wy fd, -fd)
+      d = f - o, mag = sqrt((dx dx + dy dy) + dz dz), direction d / mag."""
+    W, H, S = int(cam.hsize), int(cam.vsize), int(lens.samples)
+    n_pixels = W * H - first_pixel if n_pixels is None else n_pixels
+    if S < 1 or first_pixel < 0 or n_pixels < 0 or first_pixel + n_pixels > W * H or W * H * S >= 1 << 32:
+        raise ValueError("lens_rays: samples >= 1, a pixel window inside the frame and fewer than 2^32 rays")
+    M = camera_inverse(cam)
+    i = np.arange(first_pixel * S, (first_pixel + n_pixels) * S, dtype=np.uint64)
+    p = i // np.uint64(S)
+    py = p // np.uint64(W)
+    px = p - py * np.uint64(W)
+
+    def u(k):
+        return lens_hash(lens.seed, i, k)
+
+    def X(x, y, z):
+        return [((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3] * 1.0 for r in range(3)]
+
+    half = np.full(len(i), 0.5)
+    jx, jy = (u(0), u(1)) if lens.pixel_jitter else (half, half)
+    with np.errstate(all="ignore"):
+        wx = cam.half_width - (px.astype(np.float64) + jx) * cam.pixel_size
+        wy = cam.half_height - (py.astype(np.float64) + jy) * cam.pixel_size
+        zero = np.zeros(len(i))
+        if lens.aperture == 0.0:
+            o, f = X(zero, zero, zero), X(wx, wy, np.full(len(i), -1.0))
+        else:
+            A, B, found = zero.copy(), zero.copy(), np.zeros(len(i), bool)
+            for a in range(8):
+                ca, cb = 2.0 * u(2 + 2 * a) - 1.0, 2.0 * u(3 + 2 * a) - 1.0
+                take = ~found & (ca * ca + cb * cb <= 1.0)
+                A, B = np.where(take, ca, A), np.where(take, cb, B)
+                found |= take
+            fd = float(lens.focal_distance)
+            o, f = X(lens.aperture * A, lens.aperture * B, zero), X(wx * fd, wy * fd, np.full(len(i), -fd))
+        dx, dy, dz = f[0] - o[0], f[1] - o[1], f[2] - o[2]
+        mag = np.sqrt((dx * dx + dy * dy) + dz * dz)
+        return np.stack([o[0], o[1], o[2], dx / mag, dy / mag, dz / mag], axis=1)
+
+
+def lens_resolve(colours, samples):
+    """The lens frames' resolve step in numpy: colours (n_pixels * samples, 3) -> (n_pixels, 3), per channel
+    (((c_0 + c_1) + ...) + c_{S-1}) / float(S) — summed in increasing sample order, which matters in f64."""
+    S = int(samples)
+    c = np.ascontiguousarray(colours, np.float64).reshape(-1, S, 3)
+    with np.errstate(all="ignore"):
+        acc = c[:, 0].copy()
+        for s in range(1, S):
+            acc = acc + c[:, s]
+        return acc / float(S)
 
 
 def adaptive_mask(frame, threshold):
