@@ -539,6 +539,57 @@ int rr_render_lens(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts
 int rr_render_lens_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_lens* lens,
                           void* d_avg, void* hip_stream);
 
+/* ---- ambient occlusion: queries and frames (additive to ABI 11; test RR_HAS_AO) ----
+ * How open the surface is at a point: K short occlusion segments over the hemisphere of the normal, each answered as
+ * Scene::is_shadowed (scene.rs:234-245) answers a (point, light position) pair, and the share of them that are free.
+ * For point i (its index in the batch, or canvas sample py * hsize + px in a frame), with position P, unit normal N
+ * and k = 0..K-1, in plain f64 in exactly this order, no contraction (rray_amd.ao_directions / ao_targets / ao_resolve
+ * are the same in numpy):
+ *   hash: base = jitter_base(ao.seed, i, 0); u(k, j) = lowbias32(base ^ ((k << 21) | j)) * 2^-32 in [0, 1).  For k = 0
+ *     these are the lens frames' counters u(j): a caller who combines the two gives them different seeds.
+ *   disc point: for a = 0..7: A = 2 * u(k, 2a) - 1, B = 2 * u(k, 2a + 1) - 1; the first pair with A * A + B * B <= 1 is
+ *     taken, A = B = 0 if there is none (probability (1 - pi/4)^8, about 4.5e-6, the thin lens's rule; all eight rounds
+ *     run in every lane).  c = sqrt(1.0 - (A * A + B * B))
+ *   frame around N (Duff et al.'s branch-free basis): s = copysign(1.0, N.z); q = -1.0 / (s + N.z); b = (N.x * N.y) * q;
+ *     T = (1.0 + (s * (N.x * N.x)) * q, s * b, -(s * N.x)); Bv = (b, s + (N.y * N.y) * q, -N.y)
+ *   direction (Malley's method: cosine-weighted, never below the surface): w[r] = (A * T[r] + B * Bv[r]) + c * N[r]
+ *   segment: target[r] = P[r] + radius * w[r]; occluded(i, k) = is_shadowed(P, target), exactly what
+ *     rr_is_shadowed_device answers for that pair
+ *   value: ao(i) = (double)(K - sum_k occluded(i, k)) / (double)K.  The sum is an integer: the value does not depend on
+ *     the order in which the walks finish.
+ * rr_ao_directions: host only, no context: w of points first .. first + n - 1 (their hash indices) from n x 3 normals,
+ * as (n, K, 3) doubles, by the very function the kernel calls.
+ * rr_ao_at_device: two n x 3 double device arrays in (points, unit normals), n doubles out.  Every point is evaluated
+ * and normals are taken as unit.  rr_is_shadowed_device's conventions: enqueued on `hip_stream` (NULL: ctx stream) and
+ * NOT synchronised; frame state and rr_last_stats are left alone; n == 0 returns RR_OK; a multi-device or virtual
+ * context is RR_E_ARG; n * K >= 2^32 is RR_E_LIMIT.
+ * rr_render_ao / rr_render_ao_device: one double per canvas sample, vsize x hsize, row-major, never averaged; the rules
+ * of `opts` and the refusals are rr_render_aov's (whole frames; max_depth, seed, jitter_mode and flags are ignored),
+ * but a multi-device or virtual context is RR_E_ARG.  P and N are over_point and normalv of the sample's first hit, bit
+ * for bit rr_hit_at_device's over rr_camera_rays_device(cam); a miss writes 1.0.  The frame runs in passes of at most
+ * 2^22 pairs and at most the context's batch of points, every pass but the last a multiple of 64 points
+ * (RRAY_AO_PASS=<points> overrides, rounded up to a multiple of 64, read at context creation), in context-owned scratch
+ * that grows on demand.  Stats: samples == rays == hsize * vsize, shadow_rays == K * hits, shade_events == 0, kernel_ms
+ * one event pair around the frame.  rr_render_ao: host buffer, blocking.  rr_render_ao_device: a device buffer, enqueued
+ * and NOT synchronised, as the other _device entries.
+ * RR_E_ARG for every entry: a null pointer, samples outside 1..RR_MAX_AO_SAMPLES, reserved != 0, radius not finite or
+ * <= 0 (and n < 0, first < 0). */
+#define RR_HAS_AO 1
+#define RR_MAX_AO_SAMPLES 1024
+typedef struct {
+    int32_t samples;   /* K: occlusion rays per point, 1..RR_MAX_AO_SAMPLES */
+    int32_t reserved;  /* must be 0 */
+    double radius;     /* length of each occlusion segment; finite, > 0 */
+    uint64_t seed;
+} rr_ao;
+int rr_ao_directions(const rr_ao* ao, int64_t first, int64_t n, const double* normals, double* out_w);
+int rr_ao_at_device(rr_ctx* ctx, int64_t n, const void* d_points, const void* d_normals, const rr_ao* ao, void* d_ao,
+                    void* hip_stream);
+int rr_render_ao(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_ao* ao, double* out_ao,
+                 rr_stats* stats);
+int rr_render_ao_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_ao* ao, void* d_ao,
+                        void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

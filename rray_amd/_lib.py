@@ -84,7 +84,7 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_render_views_aov", "rr_render_views_aov_device", "rr_camera_rays_device", "rr_color_at_device",
            "rr_hit_at_device", "rr_is_shadowed_device", "rr_ray_order_device", "rr_color_at_device_ordered",
            "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
-           "rr_render_lens_device"]
+           "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -107,6 +107,14 @@ class LensDesc(C.Structure):
     """rr_lens (RR_HAS_LENS): samples per pixel, sub-pixel jitter, thin-lens aperture and focus, the samples' seed."""
     _fields_ = [("samples", C.c_int32), ("pixel_jitter", C.c_int32), ("aperture", C.c_double),
                 ("focal_distance", C.c_double), ("seed", C.c_uint64)]
+
+
+RR_MAX_AO_SAMPLES = 1024
+
+
+class AoDesc(C.Structure):
+    """rr_ao (RR_HAS_AO): occlusion rays per point, a reserved zero, the segments' length, the directions' seed."""
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double), ("seed", C.c_uint64)]
 
 
 def hit_dtype():
@@ -213,6 +221,14 @@ def lib():
                                  C.POINTER(Stats)]
     L.rr_render_lens_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(LensDesc),
                                         C.c_void_p, C.c_void_p]
+    # ambient occlusion (RR_HAS_AO)
+    L.rr_ao_directions.argtypes = [C.POINTER(AoDesc), C.c_int64, C.c_int64, _D, _D]
+    L.rr_ao_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(AoDesc), C.c_void_p,
+                                  C.c_void_p]
+    L.rr_render_ao.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AoDesc), _D,
+                               C.POINTER(Stats)]
+    L.rr_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AoDesc),
+                                      C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

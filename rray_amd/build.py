@@ -177,7 +177,7 @@ def _resources(stderr):
 
 def cross_lane_kernel(demangled):
     """device_core.inc cross_lane_ok: kernels whose walks read other lanes' registers (v_readlane)."""
-    m = re.search(r"rr::(?:listed::|views::)?(shade_kernel|persist_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|chain_kernel)<([^>]*)>",
+    m = re.search(r"rr::(?:listed::|views::)?(shade_kernel|persist_kernel|trace_kernel|n1n2_kernel|shadow_query_kernel|ao_pairs_kernel|chain_kernel)<([^>]*)>",
                   demangled)
     if not m:
         return False

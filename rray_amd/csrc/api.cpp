@@ -16,6 +16,7 @@
 #include "../../include/rray/rray.h"
 #include "device_guard.hpp"
 #include "flatten.hpp"
+#include "ao_dir.hpp"
 #include "frame_plan.hpp"
 #include "kernels.hpp"
 #include "multi.hpp"
@@ -91,6 +92,11 @@ struct rr_ctx {
     // size RRAY_LENS_PASS asks for in pixels (0: rr::plan_lens_passes' default), read at context creation
     DBuf lens_rays, lens_rgb;
     int64_t lens_pass = 0;
+    // ambient occlusion (rr_ao_at_device, rr_render_ao_device): the per-point counts of occluded pairs (4 bytes per
+    // point of a batch or a pass) and one pass's camera rays (48 bytes each; its first hits go to hitrec), grown on
+    // demand; the pass size RRAY_AO_PASS asks for in points (0: rr::plan_ao_passes' default), read at context creation
+    DBuf ao_count, ao_rays;
+    int64_t ao_pass = 0;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -845,6 +851,7 @@ int rr_create(int device, rr_ctx** out) {
     c->device = device;
     if (const char* b = std::getenv("RRAY_BATCH")) c->batch = std::max<int64_t>(1024, std::atoll(b));
     if (const char* b = std::getenv("RRAY_LENS_PASS")) c->lens_pass = std::max<int64_t>(0, std::atoll(b));
+    if (const char* b = std::getenv("RRAY_AO_PASS")) c->ao_pass = std::max<int64_t>(0, std::atoll(b));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) c->queue_budget = free_b / 2;
     if (const char* q = std::getenv("RRAY_QUEUE_BUDGET_MB")) c->queue_budget = (size_t)std::max(1ll, std::atoll(q)) << 20;
@@ -918,7 +925,8 @@ void rr_destroy(rr_ctx* c) {
                     &c->lcount, &c->hit, &c->n12, &c->n1n2, &c->ev_a, &c->ev_b, &c->canvas, &c->rays0, &c->qout, &c->tiles,
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
-                    &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb})
+                    &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb,
+                    &c->ao_count, &c->ao_rays})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2339,6 +2347,162 @@ int rr_render_lens(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, con
     rc = rr_render_lens_device(c, cam, o, lens, c->qout.p, nullptr);
     if (rc != RR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out_avg, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
+}
+
+// ---- ambient occlusion (render_ao.inc, ao_dir.hpp) ----
+// K occlusion segments per point, one lane each (ao_pairs_kernel), counted per point and resolved to (K - c) / K.  The
+// isolation rule of the ray queries holds: the query counts into the shadow sink, the frame into buffer 2, and neither
+// touches the frames' state.
+static_assert(sizeof(rr_ao) == 24, "rr_ao is 24 bytes (rray.h)");
+
+// what every AO entry refuses of the parameters; fills the kernel's argument
+static int ao_check(const rr_ao* ao, rr::DevAo* P) {
+    if (!ao) return fail(RR_E_ARG, "ambient occlusion: null rr_ao");
+    if (ao->samples < 1 || ao->samples > RR_MAX_AO_SAMPLES)
+        return fail(RR_E_ARG, "ambient-occlusion samples must be in 1.." + std::to_string(RR_MAX_AO_SAMPLES));
+    if (ao->reserved != 0) return fail(RR_E_ARG, "rr_ao.reserved must be 0");
+    if (!(std::isfinite(ao->radius) && ao->radius > 0.0)) return fail(RR_E_ARG, "the ambient-occlusion radius must be finite and > 0");
+    P->radius = ao->radius;
+    P->seed = ao->seed;
+    P->samples = (uint32_t)ao->samples;
+    P->pad = 0;
+    return RR_OK;
+}
+
+int rr_ao_directions(const rr_ao* ao, int64_t first, int64_t n, const double* normals, double* out_w) {
+    rr::DevAo P{};
+    int rc = ao_check(ao, &P);
+    if (rc != RR_OK) return rc;
+    if (first < 0 || n < 0) return fail(RR_E_ARG, "rr_ao_directions: first and n must be >= 0");
+    if (n > 0 && (!normals || !out_w)) return fail(RR_E_ARG, "rr_ao_directions: null argument");
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t base = rr::ao_base(P.seed, (uint64_t)(first + i));
+        for (uint32_t k = 0; k < P.samples; ++k)
+            rr::ao_direction(base, k, normals + 3 * i, out_w + 3 * ((size_t)i * P.samples + k));
+    }
+    return RR_OK;
+}
+
+int rr_ao_at_device(rr_ctx* c, int64_t n, const void* d_points, const void* d_normals, const rr_ao* ao, void* d_ao,
+                    void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevAo P{};
+    int rc = ao_check(ao, &P);
+    if (rc != RR_OK) return rc;
+    rc = rays_check(c, n, !d_points || !d_normals || !d_ao);
+    if (rc != RR_OK) return rc;
+    if (n * (int64_t)P.samples >= ((int64_t)1 << 32))
+        return fail(RR_E_LIMIT, "an ambient-occlusion batch must hold fewer than 2^32 pairs (n * samples)");
+    if (n == 0) return RR_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->shadow_sink.ensure(kCounterBytes));
+    HIPCHK(c->ao_count.ensure((size_t)n * sizeof(int32_t)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    const rr::AoPoints I{static_cast<const double*>(d_points), static_cast<const double*>(d_normals), 3, 1, nullptr, 0};
+    HIPCHK(rr::launch_ao_pairs(c->S, P, I, n, c->ao_count.as<int32_t>(), c->shadow_sink.as<unsigned long long>(), st));
+    HIPCHK(rr::launch_ao_resolve(c->ao_count.as<int32_t>(), ao->samples, n, static_cast<double*>(d_ao), st));
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+// what both frame entries refuse before they look at the context
+static int ao_frame_check(const rr_camera* cam, const rr_render_opts* o, const rr_ao* ao, const void* out, rr::DevAo* P) {
+    if (!cam || !o || !out) return fail(RR_E_ARG, "rr_render_ao: null argument");
+    return ao_check(ao, P);
+}
+
+int rr_render_ao_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_ao* ao, void* d_ao,
+                        void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevAo P{};
+    int rc = ao_frame_check(cam, o, ao, d_ao, &P);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "ambient-occlusion frames need a single-device context (no multi-device or virtual context)");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    rr_render_opts opts = *o;
+    opts.max_depth = 0;  // ignored here (as seed, jitter_mode and flags): no recursion in an occlusion frame
+    rc = check_opts(cam, &opts);
+    if (rc != RR_OK) return rc;
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "ambient-occlusion frames are whole frames: part 0 of 1, no band");
+    const int64_t total = cam->hsize * cam->vsize;
+    if (total >= ((int64_t)1 << 31)) return fail(RR_E_LIMIT, "an ambient-occlusion frame must hold fewer than 2^31 samples");
+    const rr::AoPassPlan plan = rr::plan_ao_passes(total, ao->samples, c->batch, c->ao_pass);
+    const int64_t pass = std::min(plan.points, total);
+    HIPCHK(hipSetDevice(c->device));
+    // one pass's camera rays, first-hit planes (RR_HIT_DOUBLES double planes, then the two int planes) and counts
+    const size_t d_bytes = (size_t)pass * rr::RR_HIT_DOUBLES * sizeof(double);
+    HIPCHK(c->ao_rays.ensure((size_t)pass * 6 * sizeof(double)));
+    HIPCHK(c->hitrec.ensure(d_bytes + (size_t)pass * 2 * sizeof(int32_t)));
+    HIPCHK(c->ao_count.ensure((size_t)pass * sizeof(int32_t)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));  // the query buffer (frame buffers keep their state)
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.rec_d = c->hitrec.as<double>();
+    O.rec_i = reinterpret_cast<int32_t*>(c->hitrec.as<char>() + d_bytes);
+    O.stride = pass;
+    rr::LevelArgs C{};
+    set_camera(C, cam);  // the frames' DevCamera and affine flag
+    rr::LevelArgs A{};   // rr_hit_at_device's level 0 on the pass's rays
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.nseg = A.nseg_out = 1;
+    A.counters = frame_counters(c, 2);
+    A.base = 0;
+    A.rays0 = c->ao_rays.as<double>();
+    // over_point and normalv are planes 12..14 and 9..11 of the records (HitOut.rec_d), object the first int plane
+    const rr::AoPoints planes{O.rec_d + 12 * pass, O.rec_d + 9 * pass, 1, pass, O.rec_i, 0};
+    for (int64_t first = 0; first < total; first += plan.points) {
+        const int64_t np = std::min(plan.points, total - first);
+        HIPCHK(rr::launch_camera_rays_window(C.cam, C.cam_affine != 0, first, np, c->ao_rays.as<double>(), st));
+        A.n = np;
+        set_level0_index(A);
+        HIPCHK(rr::launch_hit(c->S, A, O, st));
+        rr::AoPoints I = planes;
+        I.first = first;
+        HIPCHK(rr::launch_ao_pairs(c->S, P, I, np, c->ao_count.as<int32_t>(), frame_counters(c, 2), st));
+        HIPCHK(rr::launch_ao_resolve(c->ao_count.as<int32_t>(), ao->samples, np, static_cast<double*>(d_ao) + first, st));
+    }
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, total);
+    return RR_OK;
+}
+
+int rr_render_ao(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_ao* ao, double* out_ao,
+                 rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevAo P{};
+    int rc = ao_frame_check(cam, o, ao, out_ao, &P);
+    if (rc != RR_OK) return rc;
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "ambient-occlusion frames need a single-device context (no multi-device or virtual context)");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    if (cam->hsize <= 0 || cam->vsize <= 0 || cam->hsize > (1ll << 31) || cam->vsize > (1ll << 31))
+        return fail(RR_E_ARG, "bad camera size");
+    const size_t img = (size_t)cam->hsize * (size_t)cam->vsize * sizeof(double);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->qout.ensure(img));
+    rc = rr_render_ao_device(c, cam, o, ao, c->qout.p, nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out_ao, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     rr_stats local;
     rc = rr_last_stats(c, stats ? stats : &local);

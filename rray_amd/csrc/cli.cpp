@@ -10,6 +10,8 @@
 // (default 1) through a thin lens of radius A (default 0: a pinhole) focused at camera-space distance F (default 1), each
 // through the pixel centre or, with --pixel-jitter, a point uniform in the pixel (one device; not with -a, --adaptive or
 // --aov).
+// --ao-samples <K> and --ao-radius <R>, only together and only with --aov, also write <PREFIX>_ao.png: the ambient-
+// occlusion plane (rr_render_ao: K segments of length R per canvas sample), grey, per canvas sample like the other planes.
 // No CPU fallback.
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +34,8 @@ static int usage(const char* msg) {
                  "  -o, --output <OUTPUT>  Name of the output file, default is output.png [default: output.png]\n"
                  "  -a, --aa <AA>          Anti-aliasing level (default 1) (max 5) [default: 1]\n"
                  "      --aov <PREFIX>     Also write <PREFIX>_normal.png and <PREFIX>_albedo.png (first-hit planes)\n"
+                 "      --ao-samples <K>   With --aov and --ao-radius: also write <PREFIX>_ao.png, K occlusion rays per sample (1..1024)\n"
+                 "      --ao-radius <R>    With --aov and --ao-samples: length of the occlusion segments (> 0)\n"
                  "      --adaptive <THRESHOLD>  Supersample only pixels that differ from a neighbour by more than THRESHOLD\n"
                  "      --samples <S>      Lens frame: S rays per pixel (1..4096) [default: 1]\n"
                  "      --aperture <A>     Lens frame: lens radius in camera space, 0 is a pinhole [default: 0]\n"
@@ -51,8 +55,9 @@ static bool parse_usize(const char* s, long long& out) {
 
 // --aov: the normal and albedo planes of the camera rays' first hits, per canvas sample (width * aa x height * aa),
 // through the same quantisation and PNG writer as the colour image
+// ao (--ao-samples / --ao-radius; or null): also <PREFIX>_ao.png, rr_render_ao's plane as grey
 static int write_aov(const std::string& scene, long long width, long long height, int aa, int device,
-                     const std::string& prefix) {
+                     const std::string& prefix, const rr_ao* ao) {
     std::ifstream f(scene, std::ios::binary);
     std::stringstream ss;
     ss << f.rdbuf();
@@ -84,6 +89,19 @@ static int write_aov(const std::string& scene, long long width, long long height
         if (rc == RR_OK) {
             rr_quantize(albedo.data(), (int64_t)n, rgba.data());
             rc = rr_write_png((prefix + "_albedo.png").c_str(), rgba.data(), cam.hsize, cam.vsize);
+        }
+        if (rc == RR_OK && ao) {
+            rr_render_opts o{};
+            o.aa = aa;
+            o.nparts = 1;
+            o.block_rows = 8;
+            std::vector<double> plane(n);
+            rc = rr_render_ao(ctx, &cam, &o, ao, plane.data(), nullptr);
+            if (rc == RR_OK) {
+                for (size_t i = 0; i < n; ++i) albedo[3 * i] = albedo[3 * i + 1] = albedo[3 * i + 2] = plane[i];
+                rr_quantize(albedo.data(), (int64_t)n, rgba.data());
+                rc = rr_write_png((prefix + "_ao.png").c_str(), rgba.data(), cam.hsize, cam.vsize);
+            }
         }
     }
     rr_destroy(ctx);
@@ -188,6 +206,8 @@ int main(int argc, char** argv) {
     rr_lens lens{};
     lens.samples = 1;
     lens.focal_distance = 1.0;
+    rr_ao ao{};
+    bool ao_samples = false, ao_radius = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -210,6 +230,16 @@ int main(int argc, char** argv) {
         } else if (a == "--aov") {
             aov = val("--aov");
             if (aov.empty()) return usage("--aov needs a file name prefix");
+        } else if (a == "--ao-samples") {
+            long long K = 0;
+            if (!parse_usize(val("--ao-samples"), K) || K < 1 || K > RR_MAX_AO_SAMPLES)
+                return usage("--ao-samples needs a number from 1 to 1024");
+            ao.samples = (int32_t)K;
+            ao_samples = true;
+        } else if (a == "--ao-radius") {
+            if (!parse_double(val("--ao-radius"), ao.radius) || !(ao.radius > 0.0))
+                return usage("--ao-radius needs a number > 0 (the length of the occlusion segments)");
+            ao_radius = true;
         } else if (a == "--adaptive") {
             const char* v = val("--adaptive");
             char* end = nullptr;
@@ -242,6 +272,8 @@ int main(int argc, char** argv) {
     }
     if (scene.empty()) return usage("the following required arguments were not provided: --scene <SCENE>");
     if (width <= 0 || height <= 0 || aa <= 0) return usage("width, height and aa must be >= 1");
+    if ((ao_samples || ao_radius) && (!ao_samples || !ao_radius || aov.empty()))
+        return usage("--ao-samples and --ao-radius are valid only together and only with --aov <PREFIX>");
     if (lens_frame && (aa != 1 || adaptive || !aov.empty()))
         return usage("--samples, --aperture, --focus and --pixel-jitter cannot be combined with -a other than 1, --adaptive or --aov");
     std::vector<int> devices;
@@ -283,7 +315,7 @@ int main(int argc, char** argv) {
         }
     }
     if (!aov.empty()) {
-        rc = write_aov(scene, width, height, (int)aa, devices[0], aov);
+        rc = write_aov(scene, width, height, (int)aa, devices[0], aov, ao_samples ? &ao : nullptr);
         if (rc != RR_OK) {
             std::fprintf(stderr, "rray: --aov: %s (code %d)\n", rr_last_error(), rc);
             return 1;

@@ -218,6 +218,30 @@ inline LensPassPlan plan_lens_passes(int64_t n_pixels, int32_t samples, int64_t 
     return p;
 }
 
+// The pass split of rr_render_ao_device (ambient-occlusion frames): passes of whole points (canvas
+// samples), K occlusion pairs each.  Every pass but the last holds `points` points, a multiple of 64, so a pass's
+// camera rays and first hits fill whole waves.  want > 0 (RRAY_AO_PASS): that many points rounded up to a multiple of
+// 64; else the largest multiple of 64 with at most kRayPassMax pairs, and at least 64 points.  Either is then capped by
+// the context's batch rounded down to a multiple of 64 (at least 64): a pass's first hits are one launch of the
+// first-hit kernel.  Pass k holds points [k * points, min(n_points, (k + 1) * points)).
+struct AoPassPlan {
+    int64_t points;  // per pass (the last may be shorter)
+    int64_t passes;
+};
+inline AoPassPlan plan_ao_passes(int64_t n_points, int32_t samples, int64_t batch, int64_t want) {
+    AoPassPlan p{};
+    if (n_points <= 0 || samples < 1 || batch <= 0) return p;
+    if (want > 0)
+        p.points = want > ((int64_t)1 << 40) ? (int64_t)1 << 40 : (want + 63) / 64 * 64;
+    else
+        p.points = std::max<int64_t>(64, kRayPassMax / samples / 64 * 64);
+    p.points = std::min<int64_t>(p.points, std::max<int64_t>(64, batch / 64 * 64));
+    // an override never asks a launch for 2^32 pairs or more (the kernel indexes its pairs in 32 bits)
+    p.points = std::min<int64_t>(p.points, std::max<int64_t>(64, ((((int64_t)1 << 32) - 1) / samples) / 64 * 64));
+    p.passes = (n_points + p.points - 1) / p.points;
+    return p;
+}
+
 struct FramePlan {
     Family family;
     bool fused, ext;  // segmented queues between the levels; refraction halves beside the pending sums

@@ -380,4 +380,34 @@ hipError_t launch_lens_rays(const DevLens& L, int64_t first_ray, int64_t n, doub
 // lens_resolve_kernel: out[p] = (((c[p*S] + c[p*S + 1]) + ...) + c[p*S + S - 1]) / (double)S per channel, p < n_pixels
 hipError_t launch_lens_resolve(const double* colours, int32_t samples, int64_t n_pixels, double* out, hipStream_t stream);
 
+// Ambient occlusion (render_ao.inc in render_rays.hip; the definition is rray.h's RR_HAS_AO block).
+// The rr_ao parameters as ao_pairs_kernel reads them: a kernel argument of their own, never part of LevelArgs or DevScene.
+struct DevAo {
+    double radius;
+    uint64_t seed;
+    uint32_t samples, pad;  // K
+};
+// Where the points and unit normals of a launch lie: component r of point i at points[i * point_stride + r *
+// comp_stride] (normals alike) — (3, 1) for the caller's n x 3 arrays (rr_ao_at_device), (1, plane stride) for the
+// over_point / normalv planes of hit_kernel's ray-batch records (HitOut.rec_d; rr_render_ao_device).  object: the
+// records' object plane (a point with object < 0 is a miss and takes part in no walk), or null: every point is
+// evaluated.  first: the hash index of point 0 (its index in the batch or the frame).
+struct AoPoints {
+    const double* points;
+    const double* normals;
+    int64_t point_stride, comp_stride;
+    const int32_t* object;
+    int64_t first;
+};
+// ao_pairs_kernel: count[i] = the occluded ones of point i's K segments, i < n (n * K < 2^32); the walks' counters go
+// to `counters` (shadow rays: K per evaluated point).  Clears count first when K does not divide 64.
+hipError_t launch_ao_pairs(const DevScene& S, const DevAo& P, const AoPoints& I, int64_t n, int32_t* count,
+                           unsigned long long* counters, hipStream_t stream);
+// camera_rays_window_kernel: rays [first, first + n) of launch_camera_rays' batch (first + n <= hsize * vsize < 2^32),
+// ray first + j at out + 6 * j, by the same camera_ray: one pass of an occlusion frame
+hipError_t launch_camera_rays_window(const DevCamera& cam, bool affine, int64_t first, int64_t n, double* out,
+                                     hipStream_t stream);
+// ao_resolve_kernel: out[i] = (double)(K - count[i]) / (double)K, i < n
+hipError_t launch_ao_resolve(const int32_t* count, int32_t samples, int64_t n, double* out, hipStream_t stream);
+
 }  // namespace rr

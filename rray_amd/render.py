@@ -629,6 +629,34 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_avg, stream)]
         check(lib().rr_render_lens_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
 
+    # ---- ambient occlusion (rray.h RR_HAS_AO): how open the surface is at a point ----
+    def ao_at_device(self, n, d_points, d_normals, ao, d_ao, stream=None):
+        """rr_ao_at_device: the occlusion value of n points — two n x 3 f64 device arrays, positions and unit normals
+        (ints: device pointers) — into d_ao (n f64): ao_resolve of is_shadowed_device over ao_targets(points, normals,
+        ao), bit for bit.  Ordered on `stream` (int or None), not synchronised; last_stats() is left as it is."""
+        d = ao.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_points, d_normals)]
+        q = [C.c_void_p(x) if x else None for x in (d_ao, stream)]
+        check(lib().rr_ao_at_device(self.h, n, *p, C.byref(d), *q))
+
+    def render_ao(self, cam, ao, aa=1):
+        """rr_render_ao: the occlusion plane of `cam` -> dict(ao=(vsize, hsize) f64, stats): one value per canvas sample,
+        never averaged; ao_at_device at over_point / normalv of hit_at_device over camera_rays_device(cam), bit for bit,
+        1.0 where the sample misses.  stats['shadow_rays'] == ao.samples * hits."""
+        o = _lib.RenderOpts(aa, 0, 0, 0, 0, 1, 8, 0, 0, 0)
+        d = ao.desc()
+        out = np.zeros((cam.vsize, cam.hsize), np.float64)
+        st = _lib.Stats()
+        check(lib().rr_render_ao(self.h, C.byref(cam), C.byref(o), C.byref(d), _dp(out), C.byref(st)))
+        return {"ao": out, "stats": st.as_dict()}
+
+    def render_ao_device(self, cam, opts, ao, d_ao, stream=None):
+        """rr_render_ao_device: the plane into d_ao (int: a device pointer to vsize * hsize f64), ordered on `stream`
+        (int or None), not synchronised."""
+        d = ao.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_ao, stream)]
+        check(lib().rr_render_ao_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
+
 
 def _spread(q, bits, step):
     out = np.zeros(q.shape, np.uint32)
@@ -777,6 +805,66 @@ def lens_resolve(colours, samples):
         for s in range(1, S):
             acc = acc + c[:, s]
         return acc / float(S)
+
+
+class Ao:
+    """rr_ao (rray.h RR_HAS_AO): `samples` occlusion segments of length `radius` per point, cosine-weighted around the
+    normal; `seed` seeds their directions (for k = 0 the counters are the lens frames': give the two different seeds)."""
+
+    def __init__(self, samples, radius, seed=0):
+        self.samples, self.radius, self.seed = int(samples), float(radius), int(seed)
+
+    def desc(self):
+        return _lib.AoDesc(self.samples, 0, self.radius, self.seed & 0xFFFFFFFFFFFFFFFF)
+
+    def __repr__(self):
+        return f"Ao(samples={self.samples}, radius={self.radius}, seed={self.seed})"
+
+
+def ao_directions(normals, ao, first=0):
+    """The occlusion directions in numpy (rray.h RR_HAS_AO), the kernel's definition and its tests' reference: normals
+    (n, 3) f64, taken as unit -> w (n, K, 3) f64 for points first .. first + n - 1 (their hash indices).  Plain f64 in
+    this order, with u(k, j) = lens_hash(ao.seed, i, (k << 21) | j):
+      (A, B) = the first of (2 u(k, 2a) - 1, 2 u(k, 2a + 1) - 1), a = 0..7, with A A + B B <= 1, else (0, 0)
+      c = sqrt(1.0 - (A A + B B)); s = copysign(1.0, N.z); q = -1.0 / (s + N.z); b = (N.x N.y) q
+      T = (1.0 + (s (N.x N.x)) q, s b, -(s N.x)); Bv = (b, s + (N.y N.y) q, -N.y)
+      w[r] = (A T[r] + B Bv[r]) + c N[r]."""
+    N = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    n, K = len(N), int(ao.samples)
+    if K < 1 or first < 0:
+        raise ValueError("ao_directions: samples >= 1 and first >= 0")
+    i = (np.arange(n, dtype=np.uint64) + np.uint64(first))[:, None]
+    k = np.arange(K, dtype=np.uint32)[None, :] << np.uint32(21)
+    A, B, found = np.zeros((n, K)), np.zeros((n, K)), np.zeros((n, K), bool)
+    with np.errstate(all="ignore"):
+        for a in range(8):
+            ca = 2.0 * lens_hash(ao.seed, i, k | np.uint32(2 * a)) - 1.0
+            cb = 2.0 * lens_hash(ao.seed, i, k | np.uint32(2 * a + 1)) - 1.0
+            take = ~found & (ca * ca + cb * cb <= 1.0)
+            A, B = np.where(take, ca, A), np.where(take, cb, B)
+            found |= take
+        c = np.sqrt(1.0 - (A * A + B * B))
+        nx, ny, nz = N[:, 0:1], N[:, 1:2], N[:, 2:3]
+        s = np.copysign(1.0, nz)
+        q = -1.0 / (s + nz)
+        b = (nx * ny) * q
+        T = [1.0 + (s * (nx * nx)) * q, s * b, -(s * nx)]
+        Bv = [b, s + (ny * ny) * q, -ny]
+        return np.stack([(A * T[r] + B * Bv[r]) + c * N[:, r:r + 1] for r in range(3)], axis=2)
+
+
+def ao_targets(points, normals, ao, first=0):
+    """The far ends of the occlusion segments in numpy: target[i][k][r] = P[i][r] + radius * w[i][k][r], (n, K, 3) f64 —
+    point i's pairs for is_shadowed are (P[i], target[i][k])."""
+    P = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    return P[:, None, :] + float(ao.radius) * ao_directions(normals, ao, first)
+
+
+def ao_resolve(occluded, samples):
+    """The occlusion value in numpy: occluded (n * K,) or (n, K) of 0 / 1 -> (n,) f64, (K - sum_k occluded) / float(K)."""
+    K = int(samples)
+    c = np.asarray(occluded).astype(np.int64).reshape(-1, K).sum(axis=1)
+    return (K - c).astype(np.float64) / float(K)
 
 
 def adaptive_mask(frame, threshold):
