@@ -590,6 +590,71 @@ int rr_render_ao(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, 
 int rr_render_ao_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_ao* ao, void* d_ao,
                         void* hip_stream);
 
+/* ---- edge-avoiding denoiser for lens and occlusion frames (additive to ABI 11; test RR_HAS_DENOISE) ----
+ * An a-trous (hole-dilated) edge-avoiding wavelet filter over an image that is already on the device, guided by the
+ * first-hit planes of rr_render_aov.  Aimed at soft shadows, jittered pixels and occlusion planes.  Caveat: first-hit
+ * planes are the pinhole's, so with a wide aperture the filter sharpens out-of-focus edges.
+ * Inputs: the image `in`, H x W x C doubles, C in {1, 3} (an occlusion plane or a colour frame); optional guide planes
+ * of the same H x W in rr_render_aov's layouts: depth (doubles, +inf for a miss), normal (H x W x 3 doubles), object
+ * (int32, -1 for a miss), albedo (H x W x 3 doubles).
+ * Rounding: guides are rounded to float when read and widened again: z = (double)(float)depth[p], and so every normal
+ *   and albedo component.  This is part of the definition (a pixel's guides pack into 7 floats and an int32 without
+ *   changing a bit of the result).  All arithmetic is f64 in exactly the order written, no contraction.
+ * void(p): a depth plane is given and !(z_p < +inf), or an object plane is given and id_p < 0.
+ * Levels: F_0 = in.  For level i = 0..I-1: s = 2^i, sc = sigma_color * 2^-i (exact), h = (1/16, 1/4, 3/8, 1/4, 1/16).
+ * For pixel p = (x, y):
+ *   if void(p): F_{i+1}[p] = F_i[p]
+ *   else acc[c] = 0.0, ws = 0.0; for dy = -2..2 (outer), dx = -2..2 (inner), q = (x + dx * s, y + dy * s):
+ *     skip the tap if q lies outside the frame (no clamping, no mirroring), or if void(q)
+ *     w = h[dy+2] * h[dx+2]
+ *     if (dx, dy) != (0, 0), the terms that are switched on, in this order; a term whose t is not > 0.0 skips the tap
+ *     (so a NaN anywhere skips it):
+ *       1. object (RR_DN_OBJECT): id_q != id_p skips the tap
+ *       2. colour (sigma_color > 0): d_c = F_i[p][c] - F_i[q][c]; dc = (d_0 * d_0 + d_1 * d_1) + d_2 * d_2, or d_0 * d_0
+ *          for C = 1; t = 1.0 + dc / (sc * sc); w = w * (1.0 / (t * t)).  Never zero: a bright outlier is still pulled in
+ *       3. normal (sigma_normal > 0): dot = (nx_p * nx_q + ny_p * ny_q) + nz_p * nz_q; e = 1.0 - dot; if e < 0.0 then
+ *          e = 0.0; t = 1.0 - e / sigma_normal; w = w * (t * t)
+ *       4. depth (sigma_depth > 0): r = (double)(max(|dx|, |dy|) * s);
+ *          t = 1.0 - fabs(z_p - z_q) / ((sigma_depth * fabs(z_p)) * r); w = w * (t * t).  The depth change allowed
+ *          grows with the tap's distance in pixels, so a floor seen at a glancing angle is still filtered
+ *       5. albedo (sigma_albedo > 0): da = (a_0 * a_0 + a_1 * a_1) + a_2 * a_2 of the component differences;
+ *          t = 1.0 - da / (sigma_albedo * sigma_albedo); w = w * (t * t)
+ *     skip the tap unless w > 0.0
+ *     acc[c] = acc[c] + w * F_i[q][c]; ws = ws + w
+ *   F_{i+1}[p][c] = acc[c] / ws.  The centre tap always contributes 9/64, so ws > 0.  The output is F_I.
+ * (rray_amd.denoise_filter is the same in numpy.)
+ * A term that is switched on needs its plane: a null plane is RR_E_ARG.  A plane whose term is off is used only for
+ * void (depth, object) or ignored.  RR_E_ARG also: a null ctx, desc, in or out; C not 1 or 3; W or H < 1; iterations
+ * outside 1..RR_MAX_DENOISE_ITERATIONS; a sigma that is negative or not finite; unknown flag bits; `out` overlapping an
+ * input; a multi-device or virtual context.  RR_E_LIMIT: W * H >= 2^31.  No scene is needed.
+ * rr_denoise_reference: host only, no context: the definition, by the very function the kernel calls (single thread:
+ *   for small frames).
+ * rr_denoise: host buffers, runs on the device, blocking.
+ * rr_denoise_device: device buffers on the context's device, enqueued on `hip_stream` (NULL: ctx stream) and NOT
+ *   synchronised; the stream claim and device guard of the other _device entries.  One pack kernel per call, one level
+ *   kernel per iteration, through two context-owned scratch images that grow on demand (none for iterations == 1).
+ *   Frame state and rr_last_stats are left alone, as by rr_is_shadowed_device. */
+#define RR_HAS_DENOISE 1
+#define RR_MAX_DENOISE_ITERATIONS 8
+#define RR_DN_OBJECT 1 /* taps on another object id are skipped (off for meshes: every triangle is an object) */
+typedef struct {
+    int32_t iterations; /* I: 1..RR_MAX_DENOISE_ITERATIONS; level i uses holes of 2^i pixels */
+    int32_t flags;      /* RR_DN_OBJECT or 0; other bits: RR_E_ARG */
+    double sigma_color; /* each sigma finite and >= 0; 0 switches the term off */
+    double sigma_normal;
+    double sigma_depth; /* allowed relative depth change per pixel of distance */
+    double sigma_albedo;
+} rr_denoise_desc; /* 40 bytes */
+int rr_denoise_reference(const rr_denoise_desc* desc, int64_t width, int64_t height, int32_t channels, const double* in,
+                         const double* depth, const double* normal, const int32_t* object, const double* albedo,
+                         double* out);
+int rr_denoise(rr_ctx* ctx, const rr_denoise_desc* desc, int64_t width, int64_t height, int32_t channels,
+               const double* in, const double* depth, const double* normal, const int32_t* object, const double* albedo,
+               double* out);
+int rr_denoise_device(rr_ctx* ctx, const rr_denoise_desc* desc, int64_t width, int64_t height, int32_t channels,
+                      const void* d_in, const void* d_depth, const void* d_normal, const void* d_object,
+                      const void* d_albedo, void* d_out, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

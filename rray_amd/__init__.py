@@ -18,6 +18,9 @@ from .render import (  # noqa: F401
     ao_directions,
     ao_targets,
     ao_resolve,
+    Denoise,
+    denoise_reference,
+    denoise_filter,
     balance_bands,
     YamlScene,
     camera,
@@ -33,5 +36,5 @@ from .render import (  # noqa: F401
 )
 
 __all__ = ["Renderer", "SceneBuilder", "YamlScene", "camera", "part_rows", "quantize", "write_png",
-           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "ray_order_keys", "Lens", "lens_rays", "lens_resolve", "Ao", "ao_directions", "ao_targets", "ao_resolve", "RRError",
+           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "ray_order_keys", "Lens", "lens_rays", "lens_resolve", "Ao", "ao_directions", "ao_targets", "ao_resolve", "Denoise", "denoise_reference", "denoise_filter", "RRError",
            "lib"]

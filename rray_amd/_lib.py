@@ -84,7 +84,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_render_views_aov", "rr_render_views_aov_device", "rr_camera_rays_device", "rr_color_at_device",
            "rr_hit_at_device", "rr_is_shadowed_device", "rr_ray_order_device", "rr_color_at_device_ordered",
            "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
-           "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device"]
+           "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device",
+           "rr_denoise_reference", "rr_denoise", "rr_denoise_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -115,6 +116,16 @@ RR_MAX_AO_SAMPLES = 1024
 class AoDesc(C.Structure):
     """rr_ao (RR_HAS_AO): occlusion rays per point, a reserved zero, the segments' length, the directions' seed."""
     _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double), ("seed", C.c_uint64)]
+
+
+RR_MAX_DENOISE_ITERATIONS = 8
+RR_DN_OBJECT = 1
+
+
+class DenoiseDesc(C.Structure):
+    """rr_denoise_desc (RR_HAS_DENOISE): levels, flags, and the four sigmas (0 switches a term off)."""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("sigma_color", C.c_double),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
 def hit_dtype():
@@ -229,6 +240,10 @@ def lib():
                                C.POINTER(Stats)]
     L.rr_render_ao_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AoDesc),
                                       C.c_void_p, C.c_void_p]
+    # the edge-avoiding denoiser (RR_HAS_DENOISE)
+    L.rr_denoise_reference.argtypes = [C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
+    L.rr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
+    L.rr_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 7
     _lib = L
     return L
 

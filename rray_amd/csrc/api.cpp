@@ -17,6 +17,7 @@
 #include "device_guard.hpp"
 #include "flatten.hpp"
 #include "ao_dir.hpp"
+#include "denoise_tap.hpp"
 #include "frame_plan.hpp"
 #include "kernels.hpp"
 #include "multi.hpp"
@@ -97,6 +98,14 @@ struct rr_ctx {
     // demand; the pass size RRAY_AO_PASS asks for in points (0: rr::plan_ao_passes' default), read at context creation
     DBuf ao_count, ao_rays;
     int64_t ao_pass = 0;
+    // the denoiser (rr_denoise_device): the guide records (32 bytes per pixel) and the two images the levels ping-pong
+    // between (8 * channels bytes per pixel each; none for one iteration), grown on demand; dn_host: the device copies
+    // of rr_denoise's host buffers
+    DBuf dn_guides, dn_img[2], dn_host;
+    // levels with holes of at most this many pixels run the LDS-tiled kernel, the wider ones the direct kernel.  -1: the
+    // measured choice (DESIGN.md §3.22's A/B): 2 for one channel, 1 for three.  RRAY_DENOISE_LDS=<0..2> overrides (0: every
+    // level direct), read at context creation
+    int32_t dn_lds_step = -1;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -852,6 +861,8 @@ int rr_create(int device, rr_ctx** out) {
     if (const char* b = std::getenv("RRAY_BATCH")) c->batch = std::max<int64_t>(1024, std::atoll(b));
     if (const char* b = std::getenv("RRAY_LENS_PASS")) c->lens_pass = std::max<int64_t>(0, std::atoll(b));
     if (const char* b = std::getenv("RRAY_AO_PASS")) c->ao_pass = std::max<int64_t>(0, std::atoll(b));
+    if (const char* b = std::getenv("RRAY_DENOISE_LDS"))
+        c->dn_lds_step = (int32_t)std::min<long long>(rr::RR_DN_LDS_MAX_STEP, std::max<long long>(0, std::atoll(b)));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) c->queue_budget = free_b / 2;
     if (const char* q = std::getenv("RRAY_QUEUE_BUDGET_MB")) c->queue_budget = (size_t)std::max(1ll, std::atoll(q)) << 20;
@@ -926,7 +937,7 @@ void rr_destroy(rr_ctx* c) {
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
                     &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb,
-                    &c->ao_count, &c->ao_rays})
+                    &c->ao_count, &c->ao_rays, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2509,6 +2520,160 @@ int rr_render_ao(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const
     if (rc != RR_OK) return rc;
     const uint64_t nan = (stats ? stats : &local)->nan_rays;
     return nan ? nan_fail(nan) : RR_OK;
+}
+
+// ---- the edge-avoiding denoiser (render_denoise.inc, denoise_tap.hpp) ----
+// One pack kernel per call and one level kernel per iteration, through two context-owned images.  It reads no scene and
+// counts nothing: frame state and pending stats stay as they are.
+static_assert(sizeof(rr_denoise_desc) == 40, "rr_denoise_desc is 40 bytes (rray.h)");
+
+namespace {
+struct DnPlanes {
+    const void *in, *depth, *normal, *object, *albedo;
+    void* out;
+};
+bool dn_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && x < y + nb && y < x + na;
+}
+}  // namespace
+
+// what every denoiser entry refuses of its arguments (the context apart); fills the terms that are switched on
+static int dn_check(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const DnPlanes& P, int32_t* terms) {
+    if (!d || !P.in || !P.out) return fail(RR_E_ARG, "rr_denoise: null argument");
+    if (C != 1 && C != 3) return fail(RR_E_ARG, "rr_denoise: channels must be 1 or 3");
+    if (W < 1 || H < 1) return fail(RR_E_ARG, "rr_denoise: width and height must be >= 1");
+    if (d->iterations < 1 || d->iterations > RR_MAX_DENOISE_ITERATIONS)
+        return fail(RR_E_ARG, "rr_denoise: iterations must be in 1.." + std::to_string(RR_MAX_DENOISE_ITERATIONS));
+    if (d->flags & ~RR_DN_OBJECT) return fail(RR_E_ARG, "rr_denoise: unknown flag bits");
+    for (double s : {d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo})
+        if (!(std::isfinite(s) && s >= 0.0)) return fail(RR_E_ARG, "rr_denoise: every sigma must be finite and >= 0");
+    int32_t t = 0;
+    if (d->flags & RR_DN_OBJECT) t |= rr::DN_T_OBJECT;
+    if (d->sigma_color > 0.0) t |= rr::DN_T_COLOR;
+    if (d->sigma_normal > 0.0) t |= rr::DN_T_NORMAL;
+    if (d->sigma_depth > 0.0) t |= rr::DN_T_DEPTH;
+    if (d->sigma_albedo > 0.0) t |= rr::DN_T_ALBEDO;
+    if (((t & rr::DN_T_OBJECT) && !P.object) || ((t & rr::DN_T_NORMAL) && !P.normal) ||
+        ((t & rr::DN_T_DEPTH) && !P.depth) || ((t & rr::DN_T_ALBEDO) && !P.albedo))
+        return fail(RR_E_ARG, "rr_denoise: a term that is switched on needs its plane");
+    if (W > (((int64_t)1 << 31) - 1) / H) return fail(RR_E_LIMIT, "a denoised frame must hold fewer than 2^31 pixels");
+    const size_t n = (size_t)(W * H), img = n * (size_t)C * sizeof(double);
+    if (dn_overlap(P.out, img, P.in, img) || dn_overlap(P.out, img, P.depth, n * sizeof(double)) ||
+        dn_overlap(P.out, img, P.normal, n * 3 * sizeof(double)) || dn_overlap(P.out, img, P.object, n * sizeof(int32_t)) ||
+        dn_overlap(P.out, img, P.albedo, n * 3 * sizeof(double)))
+        return fail(RR_E_ARG, "rr_denoise: out overlaps an input");
+    *terms = t;
+    return RR_OK;
+}
+
+static void dn_reference_level(const rr::DnLevel& L, int64_t W, int64_t H, int32_t C, const double* src,
+                               const rr::DnGuide* g, double* dst) {
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t x = 0; x < W; ++x) {
+            if (C == 3)
+                rr::dn_pixel<3>(L, W, H, x, y, src, g, dst + 3 * (y * W + x));
+            else
+                rr::dn_pixel<1>(L, W, H, x, y, src, g, dst + (y * W + x));
+        }
+}
+
+int rr_denoise_reference(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const double* in, const double* depth,
+                         const double* normal, const int32_t* object, const double* albedo, double* out) {
+    int32_t terms = 0;
+    int rc = dn_check(d, W, H, C, DnPlanes{in, depth, normal, object, albedo, out}, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    std::vector<rr::DnGuide> g((size_t)n);
+    for (int64_t p = 0; p < n; ++p) g[(size_t)p] = rr::dn_guide(p, depth, normal, object, albedo);
+    std::vector<double> a, b;
+    if (d->iterations > 1) a.resize((size_t)n * C);
+    if (d->iterations > 2) b.resize((size_t)n * C);
+    const double* src = in;
+    for (int32_t i = 0; i < d->iterations; ++i) {
+        double* dst = i == d->iterations - 1 ? out : (i & 1 ? b.data() : a.data());
+        const rr::DnLevel L = rr::dn_level(terms, i, d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+        dn_reference_level(L, W, H, C, src, g.data(), dst);
+        src = dst;
+    }
+    return RR_OK;
+}
+
+static int dn_ctx_check(const rr_ctx* c) {
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "rr_denoise needs a single-device context (no multi-device or virtual context)");
+    return RR_OK;
+}
+
+int rr_denoise_device(rr_ctx* c, const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const void* d_in,
+                      const void* d_depth, const void* d_normal, const void* d_object, const void* d_albedo, void* d_out,
+                      void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rc = dn_check(d, W, H, C, DnPlanes{d_in, d_depth, d_normal, d_object, d_albedo, d_out}, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    const size_t img = (size_t)n * (size_t)C * sizeof(double);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the scratch is claimed before it may grow: a call on another stream may still read the buffers that ensure frees
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    if (c->dn_guides.bytes < (size_t)n * sizeof(rr::DnGuide) || (d->iterations > 1 && c->dn_img[0].bytes < img) ||
+        (d->iterations > 2 && c->dn_img[1].bytes < img))
+        HIPCHK(hipStreamSynchronize(st));  // growing frees: nothing enqueued may still use the old buffers
+    HIPCHK(c->dn_guides.ensure((size_t)n * sizeof(rr::DnGuide)));
+    if (d->iterations > 1) HIPCHK(c->dn_img[0].ensure(img));
+    if (d->iterations > 2) HIPCHK(c->dn_img[1].ensure(img));
+    rr::DnGuide* g = c->dn_guides.as<rr::DnGuide>();
+    HIPCHK(rr::launch_denoise_pack(n, static_cast<const double*>(d_depth), static_cast<const double*>(d_normal),
+                                   static_cast<const int32_t*>(d_object), static_cast<const double*>(d_albedo), g, st));
+    const double* src = static_cast<const double*>(d_in);
+    const int32_t lds_step = c->dn_lds_step >= 0 ? c->dn_lds_step : (C == 1 ? 2 : 1);
+    for (int32_t i = 0; i < d->iterations; ++i) {
+        double* dst = i == d->iterations - 1 ? static_cast<double*>(d_out) : c->dn_img[i & 1].as<double>();
+        const rr::DnLevel L = rr::dn_level(terms, i, d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+        HIPCHK(rr::launch_denoise_level(L, L.step <= lds_step, C, W, H, src, g, dst, st));
+        src = dst;
+    }
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+int rr_denoise(rr_ctx* c, const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const double* in, const double* depth,
+               const double* normal, const int32_t* object, const double* albedo, double* out) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rc = dn_check(d, W, H, C, DnPlanes{in, depth, normal, object, albedo, out}, &terms);
+    if (rc != RR_OK) return rc;
+    const size_t n = (size_t)(W * H);
+    // one device block: out, in, then the planes that are given, each 256-byte aligned
+    const void* host[5] = {in, depth, normal, object, albedo};
+    const size_t bytes[5] = {n * C * sizeof(double), n * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t),
+                             n * 3 * sizeof(double)};
+    size_t off[6], total = (bytes[0] + 255) & ~(size_t)255;  // out first
+    for (int k = 0; k < 5; ++k) {
+        off[k] = total;
+        if (host[k]) total += (bytes[k] + 255) & ~(size_t)255;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_ctx(c));  // dn_host may grow, and a call on another stream may still read it
+    HIPCHK(c->dn_host.ensure(total));
+    char* base = c->dn_host.as<char>();
+    const void* dev[5];
+    for (int k = 0; k < 5; ++k) {
+        dev[k] = host[k] ? base + off[k] : nullptr;
+        if (host[k]) HIPCHK(hipMemcpyAsync(base + off[k], host[k], bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    rc = rr_denoise_device(c, d, W, H, C, dev[0], dev[1], dev[2], dev[3], dev[4], base, nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, base, bytes[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RR_OK;
 }
 
 }  // extern "C"

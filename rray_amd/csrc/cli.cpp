@@ -12,6 +12,10 @@
 // --aov).
 // --ao-samples <K> and --ao-radius <R>, only together and only with --aov, also write <PREFIX>_ao.png: the ambient-
 // occlusion plane (rr_render_ao: K segments of length R per canvas sample), grey, per canvas sample like the other planes.
+// --denoise <I> filters a stochastic image with rr_denoise (I a-trous levels guided by the first-hit planes of the same
+// camera; --denoise-color <sigma> adds the colour term, the other sigmas are the library's defaults 0.25 / 0.05 / 0.1):
+// with --samples the lens frame's colour image, with --ao-samples the <PREFIX>_ao.png plane.  Not with -a other than 1
+// or --adaptive.
 // No CPU fallback.
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +45,8 @@ static int usage(const char* msg) {
                  "      --aperture <A>     Lens frame: lens radius in camera space, 0 is a pinhole [default: 0]\n"
                  "      --focus <F>        Lens frame: camera-space distance of the plane in focus [default: 1]\n"
                  "      --pixel-jitter     Lens frame: each sample through a point uniform in its pixel\n"
+                 "      --denoise <I>      With --samples or --ao-samples: filter the lens frame / the _ao.png plane, I levels (1..8)\n"
+                 "      --denoise-color <SIGMA>  With --denoise: switch the colour term on (>= 0) [default: 0]\n"
                  "  -h, --help             Print help\n  -V, --version          Print version\n");
     return 2;
 }
@@ -56,8 +62,9 @@ static bool parse_usize(const char* s, long long& out) {
 // --aov: the normal and albedo planes of the camera rays' first hits, per canvas sample (width * aa x height * aa),
 // through the same quantisation and PNG writer as the colour image
 // ao (--ao-samples / --ao-radius; or null): also <PREFIX>_ao.png, rr_render_ao's plane as grey
+// dn (--denoise; or null): the occlusion plane goes through rr_denoise with the four first-hit planes first
 static int write_aov(const std::string& scene, long long width, long long height, int aa, int device,
-                     const std::string& prefix, const rr_ao* ao) {
+                     const std::string& prefix, const rr_ao* ao, const rr_denoise_desc* dn) {
     std::ifstream f(scene, std::ios::binary);
     std::stringstream ss;
     ss << f.rdbuf();
@@ -69,14 +76,31 @@ static int write_aov(const std::string& scene, long long width, long long height
     rc = rr_create(device, &ctx);
     if (rc == RR_OK) rc = rr_scene_upload(ctx, rr_scene_desc_of(S));
     const size_t n = (size_t)cam.hsize * (size_t)cam.vsize;
-    std::vector<double> normal(n * 3), albedo(n * 3);
+    std::vector<double> normal(n * 3), albedo(n * 3), plane, depth;
+    std::vector<int32_t> object;
     if (rc == RR_OK) {
         rr_render_opts o{};
         o.aa = aa;
         o.nparts = 1;
         o.block_rows = 8;
-        rc = rr_render_aov(ctx, &cam, &o, RR_AOV_NORMAL | RR_AOV_ALBEDO, nullptr, normal.data(), nullptr, albedo.data(),
-                           nullptr);
+        if (ao && dn) {
+            depth.resize(n);
+            object.resize(n);
+            rc = rr_render_aov(ctx, &cam, &o, RR_AOV_DEPTH | RR_AOV_NORMAL | RR_AOV_OBJECT | RR_AOV_ALBEDO, depth.data(),
+                               normal.data(), object.data(), albedo.data(), nullptr);
+        } else {
+            rc = rr_render_aov(ctx, &cam, &o, RR_AOV_NORMAL | RR_AOV_ALBEDO, nullptr, normal.data(), nullptr, albedo.data(),
+                               nullptr);
+        }
+        if (rc == RR_OK && ao) {
+            plane.resize(n);
+            rc = rr_render_ao(ctx, &cam, &o, ao, plane.data(), nullptr);
+            if (rc == RR_OK && dn) {  // filtered before the normals are remapped for their PNG
+                std::vector<double> raw = plane;
+                rc = rr_denoise(ctx, dn, cam.hsize, cam.vsize, 1, raw.data(), depth.data(), normal.data(), object.data(),
+                                albedo.data(), plane.data());
+            }
+        }
     }
     if (rc == RR_OK) {
         std::vector<uint8_t> rgba(n * 4);
@@ -91,17 +115,9 @@ static int write_aov(const std::string& scene, long long width, long long height
             rc = rr_write_png((prefix + "_albedo.png").c_str(), rgba.data(), cam.hsize, cam.vsize);
         }
         if (rc == RR_OK && ao) {
-            rr_render_opts o{};
-            o.aa = aa;
-            o.nparts = 1;
-            o.block_rows = 8;
-            std::vector<double> plane(n);
-            rc = rr_render_ao(ctx, &cam, &o, ao, plane.data(), nullptr);
-            if (rc == RR_OK) {
-                for (size_t i = 0; i < n; ++i) albedo[3 * i] = albedo[3 * i + 1] = albedo[3 * i + 2] = plane[i];
-                rr_quantize(albedo.data(), (int64_t)n, rgba.data());
-                rc = rr_write_png((prefix + "_ao.png").c_str(), rgba.data(), cam.hsize, cam.vsize);
-            }
+            for (size_t i = 0; i < n; ++i) albedo[3 * i] = albedo[3 * i + 1] = albedo[3 * i + 2] = plane[i];
+            rr_quantize(albedo.data(), (int64_t)n, rgba.data());
+            rc = rr_write_png((prefix + "_ao.png").c_str(), rgba.data(), cam.hsize, cam.vsize);
         }
     }
     rr_destroy(ctx);
@@ -153,9 +169,10 @@ static int render_adaptive(const std::string& scene, long long width, long long 
 }
 
 // --samples / --aperture / --focus / --pixel-jitter: the colour image through rr_render_lens (camera.rs:113's depth 5
-// and seed 0, as the plain path)
+// and seed 0, as the plain path); dn (--denoise; or null): the frame goes through rr_denoise with the aa 1 first-hit
+// planes of the same camera before it is quantised
 static int render_lens(const std::string& scene, long long width, long long height, int device, const rr_lens& lens,
-                       const std::string& output) {
+                       const rr_denoise_desc* dn, const std::string& output) {
     std::ifstream f(scene, std::ios::binary);
     if (!f) {  // scene_builder_yaml.rs:434 panics "File does not exist"
         std::fprintf(stderr, "rray: File does not exist (code %d)\n", RR_E_IO);
@@ -178,6 +195,15 @@ static int render_lens(const std::string& scene, long long width, long long heig
         o.nparts = 1;
         o.block_rows = 8;
         rc = rr_render_lens(ctx, &cam, &o, &lens, avg.data(), nullptr);
+        if (rc == RR_OK && dn) {
+            std::vector<double> raw = avg, depth(n), normal(n * 3), albedo(n * 3);
+            std::vector<int32_t> object(n);
+            rc = rr_render_aov(ctx, &cam, &o, RR_AOV_DEPTH | RR_AOV_NORMAL | RR_AOV_OBJECT | RR_AOV_ALBEDO, depth.data(),
+                               normal.data(), object.data(), albedo.data(), nullptr);
+            if (rc == RR_OK)
+                rc = rr_denoise(ctx, dn, width, height, 3, raw.data(), depth.data(), normal.data(), object.data(),
+                                albedo.data(), avg.data());
+        }
     }
     if (rc == RR_OK) {
         std::vector<uint8_t> rgba(n * 4);
@@ -208,6 +234,11 @@ int main(int argc, char** argv) {
     lens.focal_distance = 1.0;
     rr_ao ao{};
     bool ao_samples = false, ao_radius = false;
+    rr_denoise_desc dn{};  // the library's defaults (rray_amd.Denoise): no colour term, no object term
+    dn.sigma_normal = 0.25;
+    dn.sigma_depth = 0.05;
+    dn.sigma_albedo = 0.1;
+    bool denoise = false, denoise_color = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -240,6 +271,16 @@ int main(int argc, char** argv) {
             if (!parse_double(val("--ao-radius"), ao.radius) || !(ao.radius > 0.0))
                 return usage("--ao-radius needs a number > 0 (the length of the occlusion segments)");
             ao_radius = true;
+        } else if (a == "--denoise") {
+            long long I = 0;
+            if (!parse_usize(val("--denoise"), I) || I < 1 || I > RR_MAX_DENOISE_ITERATIONS)
+                return usage("--denoise needs a number of levels from 1 to 8");
+            dn.iterations = (int32_t)I;
+            denoise = true;
+        } else if (a == "--denoise-color") {
+            if (!parse_double(val("--denoise-color"), dn.sigma_color) || dn.sigma_color < 0.0)
+                return usage("--denoise-color needs a number >= 0 (the colour sigma)");
+            denoise_color = true;
         } else if (a == "--adaptive") {
             const char* v = val("--adaptive");
             char* end = nullptr;
@@ -274,6 +315,11 @@ int main(int argc, char** argv) {
     if (width <= 0 || height <= 0 || aa <= 0) return usage("width, height and aa must be >= 1");
     if ((ao_samples || ao_radius) && (!ao_samples || !ao_radius || aov.empty()))
         return usage("--ao-samples and --ao-radius are valid only together and only with --aov <PREFIX>");
+    if (denoise_color && !denoise) return usage("--denoise-color is valid only with --denoise <I>");
+    if (denoise && (aa != 1 || adaptive))
+        return usage("--denoise cannot be combined with -a other than 1 or with --adaptive");
+    if (denoise && !lens_frame && !ao_samples)
+        return usage("--denoise filters a lens frame (--samples) or an occlusion plane (--ao-samples): give one of them");
     if (lens_frame && (aa != 1 || adaptive || !aov.empty()))
         return usage("--samples, --aperture, --focus and --pixel-jitter cannot be combined with -a other than 1, --adaptive or --aov");
     std::vector<int> devices;
@@ -302,7 +348,7 @@ int main(int argc, char** argv) {
     int rc;
     if (lens_frame) {
         if (devices.size() != 1) return usage("a lens frame renders on one device");
-        if (render_lens(scene, width, height, devices[0], lens, output) != RR_OK) return 1;
+        if (render_lens(scene, width, height, devices[0], lens, denoise ? &dn : nullptr, output) != RR_OK) return 1;
     } else if (adaptive) {
         if (devices.size() != 1) return usage("--adaptive renders on one device");
         if (render_adaptive(scene, width, height, (int)aa, devices[0], threshold, output) != RR_OK) return 1;
@@ -315,7 +361,7 @@ int main(int argc, char** argv) {
         }
     }
     if (!aov.empty()) {
-        rc = write_aov(scene, width, height, (int)aa, devices[0], aov, ao_samples ? &ao : nullptr);
+        rc = write_aov(scene, width, height, (int)aa, devices[0], aov, ao_samples ? &ao : nullptr, denoise ? &dn : nullptr);
         if (rc != RR_OK) {
             std::fprintf(stderr, "rray: --aov: %s (code %d)\n", rr_last_error(), rc);
             return 1;

@@ -410,4 +410,18 @@ hipError_t launch_camera_rays_window(const DevCamera& cam, bool affine, int64_t 
 // ao_resolve_kernel: out[i] = (double)(K - count[i]) / (double)K, i < n
 hipError_t launch_ao_resolve(const int32_t* count, int32_t samples, int64_t n, double* out, hipStream_t stream);
 
+// The edge-avoiding denoiser (render_denoise.inc in render_rays.hip; the definition is rray.h's
+// RR_HAS_DENOISE block, its arithmetic denoise_tap.hpp's).
+struct DnGuide;
+struct DnLevel;
+// denoise_pack_kernel: guides[p] = dn_guide(p, ...) for p < n (n < 2^31); a null plane packs as zeros
+hipError_t launch_denoise_pack(int64_t n, const double* depth, const double* normal, const int32_t* object,
+                               const double* albedo, DnGuide* guides, hipStream_t stream);
+// denoise_level_kernel<channels>: dst = one level of the filter over src (W x H x channels doubles, channels 1 or 3,
+// W * H < 2^31, src != dst) with the records of launch_denoise_pack.  lds: levels with holes of 1 or 2 pixels run
+// denoise_level_lds_kernel (tile and halo staged in LDS; the same result bit for bit), wider ones the direct kernel.
+constexpr int RR_DN_LDS_MAX_STEP = 2;
+hipError_t launch_denoise_level(const DnLevel& L, bool lds, int32_t channels, int64_t W, int64_t H, const double* src,
+                                const DnGuide* guides, double* dst, hipStream_t stream);
+
 }  // namespace rr

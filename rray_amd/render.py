@@ -657,6 +657,24 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_ao, stream)]
         check(lib().rr_render_ao_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
 
+    # ---- the edge-avoiding denoiser (rray.h RR_HAS_DENOISE) ----
+    def denoise(self, img, dn, depth=None, normal=None, object=None, albedo=None):
+        """rr_denoise: `img` (H, W) or (H, W, 1) or (H, W, 3) f64 filtered on the device with the guide planes that are
+        given (render_aov's layouts) -> an array of img's shape; denoise_filter of the same arguments, bit for bit."""
+        a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+        out = np.zeros_like(a)
+        d = dn.desc()
+        check(lib().rr_denoise(self.h, C.byref(d), W, H, Cn, _dp(a), *_denoise_ptrs(planes), _dp(out)))
+        return out.reshape(np.shape(img))
+
+    def denoise_device(self, dn, width, height, channels, d_in, d_out, d_depth=None, d_normal=None, d_object=None,
+                       d_albedo=None, stream=None):
+        """rr_denoise_device: device buffers (ints: device pointers; d_in and d_out height * width * channels f64),
+        ordered on `stream` (int or None), not synchronised; last_stats() is left as it is."""
+        d = dn.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_in, d_depth, d_normal, d_object, d_albedo, d_out, stream)]
+        check(lib().rr_denoise_device(self.h, C.byref(d), width, height, channels, *p))
+
 
 def _spread(q, bits, step):
     out = np.zeros(q.shape, np.uint32)
@@ -865,6 +883,149 @@ def ao_resolve(occluded, samples):
     K = int(samples)
     c = np.asarray(occluded).astype(np.int64).reshape(-1, K).sum(axis=1)
     return (K - c).astype(np.float64) / float(K)
+
+
+class Denoise:
+    """rr_denoise_desc (rray.h RR_HAS_DENOISE): `iterations` a-trous levels (level i has holes of 2^i pixels); a sigma
+    of 0 switches its term off; object=True skips taps on another object id (leave it off for meshes: every triangle
+    is an object)."""
+
+    def __init__(self, iterations, sigma_color=0.0, sigma_normal=0.25, sigma_depth=0.05, sigma_albedo=0.1, object=False):
+        self.iterations = int(iterations)
+        self.sigma_color, self.sigma_normal = float(sigma_color), float(sigma_normal)
+        self.sigma_depth, self.sigma_albedo = float(sigma_depth), float(sigma_albedo)
+        self.object = bool(object)
+
+    def desc(self):
+        return _lib.DenoiseDesc(self.iterations, _lib.RR_DN_OBJECT if self.object else 0, self.sigma_color,
+                                self.sigma_normal, self.sigma_depth, self.sigma_albedo)
+
+    def __repr__(self):
+        return (f"Denoise(iterations={self.iterations}, sigma_color={self.sigma_color}, sigma_normal={self.sigma_normal}, "
+                f"sigma_depth={self.sigma_depth}, sigma_albedo={self.sigma_albedo}, object={self.object})")
+
+
+def _denoise_args(img, depth, normal, object, albedo):
+    """The image as a contiguous (H, W, C) f64 array, the planes as contiguous arrays of rr_denoise's types (None stays
+    None), and (H, W, C)."""
+    a = np.ascontiguousarray(img, np.float64)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.ndim != 3:
+        raise ValueError("denoise: the image is (H, W), (H, W, 1) or (H, W, 3)")
+    H, W, Cn = a.shape
+    planes = {"depth": (depth, np.float64, (H, W)), "normal": (normal, np.float64, (H, W, 3)),
+              "object": (object, np.int32, (H, W)), "albedo": (albedo, np.float64, (H, W, 3))}
+    out = {}
+    for k, (v, t, shape) in planes.items():
+        if v is None:
+            out[k] = None
+            continue
+        v = np.ascontiguousarray(v, t)
+        if v.shape != shape:
+            raise ValueError(f"denoise: the {k} plane has shape {v.shape}, the image needs {shape}")
+        out[k] = v
+    return a, out, (H, W, Cn)
+
+
+def _denoise_ptrs(planes):
+    return [None if planes[k] is None else (_ip(planes[k]) if k == "object" else _dp(planes[k]))
+            for k in ("depth", "normal", "object", "albedo")]
+
+
+def denoise_reference(img, dn, depth=None, normal=None, object=None, albedo=None):
+    """rr_denoise_reference: the C definition on the host (single thread, no device), by the function the kernel calls."""
+    a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+    out = np.zeros_like(a)
+    d = dn.desc()
+    check(lib().rr_denoise_reference(C.byref(d), W, H, Cn, _dp(a), *_denoise_ptrs(planes), _dp(out)))
+    return out.reshape(np.shape(img))
+
+
+def denoise_filter(img, dn, depth=None, normal=None, object=None, albedo=None):
+    """The denoiser in numpy (rray.h RR_HAS_DENOISE), the kernel's definition and its tests' reference, vectorised over
+    the frame: 25 shifted slices per level.  Guides are rounded to f32 and widened; plain f64 in the header's order:
+      void(p): depth given and not z_p < inf, or object given and id_p < 0; a void pixel keeps its value
+      per level i (s = 2^i, sc = sigma_color 2^-i), taps dy = -2..2 (outer), dx = -2..2 (inner), q = p + (dx s, dy s)
+      inside the frame and not void: w = h[dy+2] h[dx+2]; off-centre taps take the terms that are on, each skipping the
+      tap unless its t > 0: object (id_q == id_p); colour t = 1 + dc / (sc sc), w *= 1 / (t t); normal
+      t = 1 - max(1 - dot, 0) / sigma_normal, w *= t t; depth t = 1 - |z_p - z_q| / ((sigma_depth |z_p|) max(|dx|,|dy|) s);
+      albedo t = 1 - da / (sigma_albedo sigma_albedo); taps with w > 0 add w F[q] to acc and w to ws; F' = acc / ws."""
+    a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+    I = int(dn.iterations)
+    sig = (dn.sigma_color, dn.sigma_normal, dn.sigma_depth, dn.sigma_albedo)
+    if not 1 <= I <= _lib.RR_MAX_DENOISE_ITERATIONS or Cn not in (1, 3) or W < 1 or H < 1:
+        raise ValueError("denoise_filter: iterations in 1..8, 1 or 3 channels, a frame of at least one pixel")
+    if not all(math.isfinite(x) and x >= 0.0 for x in sig):
+        raise ValueError("denoise_filter: every sigma is finite and >= 0")
+    on_c, on_n, on_z, on_a = (x > 0.0 for x in sig)
+    if (dn.object and planes["object"] is None) or (on_n and planes["normal"] is None) or \
+            (on_z and planes["depth"] is None) or (on_a and planes["albedo"] is None):
+        raise ValueError("denoise_filter: a term that is switched on needs its plane")
+    with np.errstate(all="ignore"):
+        f32 = lambda v: None if v is None else v.astype(np.float32).astype(np.float64)  # noqa: E731
+        z, nrm, alb, ids = f32(planes["depth"]), f32(planes["normal"]), f32(planes["albedo"]), planes["object"]
+        void = np.zeros((H, W), bool)
+        if z is not None:
+            void |= ~(z < np.inf)
+        if ids is not None:
+            void |= ids < 0
+        h = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+        F = a
+        for i in range(I):
+            s = 1 << i
+            sc = dn.sigma_color * (1.0 / float(s))
+            sc2 = np.float64(sc) * np.float64(sc)
+            sa2 = np.float64(dn.sigma_albedo) * np.float64(dn.sigma_albedo)
+            acc = np.zeros((H, W, Cn))
+            ws = np.zeros((H, W))
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    ox, oy = dx * s, dy * s
+                    if abs(ox) >= W or abs(oy) >= H:
+                        continue
+                    # p over the pixels whose tap lies inside the frame, q the tap
+                    P = (slice(max(0, -oy), H - max(0, oy)), slice(max(0, -ox), W - max(0, ox)))
+                    Q = (slice(max(0, oy), H - max(0, -oy)), slice(max(0, ox), W - max(0, -ox)))
+                    ok = ~void[P] & ~void[Q]
+                    w = np.full(ok.shape, h[dy + 2] * h[dx + 2])
+                    Fp, Fq = F[P], F[Q]
+                    if dx or dy:
+                        if dn.object:
+                            ok &= ids[Q] == ids[P]
+                        if on_c:
+                            d = Fp - Fq
+                            dc = d[..., 0] * d[..., 0]
+                            if Cn == 3:
+                                dc = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                            t = 1.0 + dc / sc2
+                            ok &= t > 0.0
+                            w = w * (1.0 / (t * t))
+                        if on_n:
+                            np_, nq = nrm[P], nrm[Q]
+                            dot = (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2]
+                            e = 1.0 - dot
+                            e = np.where(e < 0.0, 0.0, e)
+                            t = 1.0 - e / dn.sigma_normal
+                            ok &= t > 0.0
+                            w = w * (t * t)
+                        if on_z:
+                            r = float(max(abs(dx), abs(dy)) * s)
+                            t = 1.0 - np.abs(z[P] - z[Q]) / ((dn.sigma_depth * np.abs(z[P])) * r)
+                            ok &= t > 0.0
+                            w = w * (t * t)
+                        if on_a:
+                            da_ = alb[P] - alb[Q]
+                            da = (da_[..., 0] * da_[..., 0] + da_[..., 1] * da_[..., 1]) + da_[..., 2] * da_[..., 2]
+                            t = 1.0 - da / sa2
+                            ok &= t > 0.0
+                            w = w * (t * t)
+                    ok &= w > 0.0
+                    # a tap that is skipped adds nothing: x + 0.0 keeps every x the sums can hold (they are never -0.0)
+                    acc[P] = np.where(ok[..., None], acc[P] + w[..., None] * Fq, acc[P])
+                    ws[P] = np.where(ok, ws[P] + w, ws[P])
+            F = np.where(void[..., None], F, acc / np.where(void, 1.0, ws)[..., None])
+    return F.reshape(np.shape(img))
 
 
 def adaptive_mask(frame, threshold):
