@@ -655,6 +655,62 @@ int rr_denoise_device(rr_ctx* ctx, const rr_denoise_desc* desc, int64_t width, i
                       const void* d_in, const void* d_depth, const void* d_normal, const void* d_object,
                       const void* d_albedo, void* d_out, void* hip_stream);
 
+/* ---- one-bounce indirect light: gathered radiance at points and frames (additive to ABI 11; test RR_HAS_INDIRECT) ----
+ * What the surroundings send to a diffuse surface: the mean of the colours that K cosine-weighted rays from the point
+ * bring back, each answered as rr_color_at_device answers any ray.  (rr_render_gather_device is the multi-device frame
+ * gather; this feature is called "indirect" everywhere.)  For point i (its index in the batch, or canvas sample
+ * py * hsize + px in a frame), with position P, unit normal N and k = 0..K-1 (rray_amd.indirect_rays /
+ * indirect_resolve are the same in numpy):
+ *   direction: w(i, k) = ao_direction(ao_base(ind.seed, i), k, N): the very function the ambient-occlusion block above
+ *     defines and calls — same hash, same disc rejection, same basis, same operation order.  (A caller who combines
+ *     the two, or the lens frames, gives them different seeds.)
+ *   ray: ray j = i * K + k has origin P and direction w(i, k), taken as it is, with no renormalisation; six doubles in
+ *     rr_camera_rays_device's layout.
+ *   radiance: L(i, k) is what rr_color_at_device writes for ray j of that batch with remaining = ind.remaining and the
+ *     call's seed and jitter_mode: the area lights' jitter identity is sample j, path 1.
+ *   value: G(i)[c] = (((L(i,0)[c] + L(i,1)[c]) + ...) + L(i,K-1)[c]) / (double)K, three doubles, plain f64 in this
+ *     order.  With cosine-weighted directions this is the irradiance divided by pi.  It is NOT multiplied by the
+ *     surface's own albedo, which is what rr_denoise wants; rray_amd.indirect_compose adds it to a colour frame.
+ *   The plain ray entries' caveat (the ordered-batch block above) carries over: in a wave that mixes shininess values a
+ *   specular term may move by an ulp with the wave's composition, and a frame's waves hold only the rays of the samples
+ *   that hit.  In a scene whose materials share one shininess every value is bit for bit the composition's.
+ * rr_indirect_at_device: two n x 3 double device arrays in (points, unit normals), n x 3 doubles out.  Every point is
+ *   evaluated and normals are taken as unit.  rr_ao_at_device's conventions: enqueued on `hip_stream` (NULL: ctx
+ *   stream) and NOT synchronised; frame state is left alone; n == 0 returns RR_OK; a multi-device or virtual context
+ *   is RR_E_ARG; n * K >= 2^32 is RR_E_LIMIT.  rr_last_stats afterwards is rr_color_at_device's over the n * K rays,
+ *   with samples == n.  The batch runs in passes of whole points (at most 2^22 rays and at most the context's batch
+ *   of points, a multiple of 64 points each but the last; RRAY_INDIRECT_PASS=<points> overrides, rounded up to a
+ *   multiple of 64, read at context creation) through context-owned scratch that grows on demand and never exceeds one
+ *   pass: 48 + 24 bytes per ray.
+ * rr_render_indirect / rr_render_indirect_device: vsize x hsize x 3 doubles, one value per canvas sample, row-major,
+ *   never averaged.  The rules of `opts` and the refusals are rr_render_ao's (whole frames; a multi-device or virtual
+ *   context is RR_E_ARG); opts->seed and opts->jitter_mode are the trace's; max_depth and flags are ignored.  P and N
+ *   are over_point and normalv of the sample's first hit, bit for bit rr_hit_at_device's over
+ *   rr_camera_rays_device(cam).  A miss writes (0, 0, 0) and traces nothing: the gathered rays of a pass are listed on
+ *   the device, only the samples that hit, and their number never visits the host.  hsize * vsize * K >= 2^32 is
+ *   RR_E_LIMIT.  Passes as above (a frame's scratch adds 4 bytes per ray for the list).  Stats: samples == hsize *
+ *   vsize; rays, shadow_rays, shade_events, n1n2_scans and nan_rays are each what rr_hit_at_device reports over the
+ *   camera's rays plus what rr_color_at_device reports over the K rays of the samples that hit, and only those;
+ *   kernel_ms is one event pair around the frame.  rr_render_indirect: host buffer, blocking, RR_E_NAN after writing
+ *   when nan_rays > 0.  rr_render_indirect_device: a device buffer, enqueued and NOT synchronised; NaN rays are
+ *   reported through the stats only.  The frames are served by the in-wave kernels only: RR_E_ARG under RRAY_UNFUSED /
+ *   RRAY_NO_TREE / RRAY_NO_CHAIN, as rr_color_at_device_ordered; the point query has no list and serves there too.
+ * RR_E_ARG for every entry: a null pointer, samples outside 1..RR_MAX_INDIRECT_SAMPLES (and n < 0).  RR_E_LIMIT:
+ * remaining outside 0..RR_MAX_DEPTH. */
+#define RR_HAS_INDIRECT 1
+#define RR_MAX_INDIRECT_SAMPLES 1024
+typedef struct {
+    int32_t samples;   /* K: gathered rays per point, 1..RR_MAX_INDIRECT_SAMPLES */
+    int32_t remaining; /* the gathered rays' `remaining` (reflection / refraction budget), 0..RR_MAX_DEPTH */
+    uint64_t seed;     /* seed of the directions (the area lights keep the call's own seed) */
+} rr_indirect;         /* 16 bytes */
+int rr_indirect_at_device(rr_ctx* ctx, int64_t n, const void* d_points, const void* d_normals, const rr_indirect* ind,
+                          uint64_t seed, int32_t jitter_mode, void* d_out, void* hip_stream);
+int rr_render_indirect(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_indirect* ind,
+                       double* out, rr_stats* stats);
+int rr_render_indirect_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_indirect* ind,
+                              void* d_out, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

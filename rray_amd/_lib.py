@@ -85,7 +85,8 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_hit_at_device", "rr_is_shadowed_device", "rr_ray_order_device", "rr_color_at_device_ordered",
            "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
            "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device",
-           "rr_denoise_reference", "rr_denoise", "rr_denoise_device"]
+           "rr_denoise_reference", "rr_denoise", "rr_denoise_device", "rr_indirect_at_device", "rr_render_indirect",
+           "rr_render_indirect_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -126,6 +127,14 @@ class DenoiseDesc(C.Structure):
     """rr_denoise_desc (RR_HAS_DENOISE): levels, flags, and the four sigmas (0 switches a term off)."""
     _fields_ = [("iterations", C.c_int32), ("flags", C.c_int32), ("sigma_color", C.c_double),
                 ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
+
+
+RR_MAX_INDIRECT_SAMPLES = 1024
+
+
+class IndirectDesc(C.Structure):
+    """rr_indirect (RR_HAS_INDIRECT): gathered rays per point, their `remaining`, the directions' seed."""
+    _fields_ = [("samples", C.c_int32), ("remaining", C.c_int32), ("seed", C.c_uint64)]
 
 
 def hit_dtype():
@@ -244,6 +253,13 @@ def lib():
     L.rr_denoise_reference.argtypes = [C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
     L.rr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
     L.rr_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 7
+    # one-bounce indirect light (RR_HAS_INDIRECT)
+    L.rr_indirect_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(IndirectDesc),
+                                        C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]
+    L.rr_render_indirect.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(IndirectDesc), _D,
+                                     C.POINTER(Stats)]
+    L.rr_render_indirect_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderOpts),
+                                            C.POINTER(IndirectDesc), C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

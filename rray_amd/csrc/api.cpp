@@ -98,6 +98,13 @@ struct rr_ctx {
     // demand; the pass size RRAY_AO_PASS asks for in points (0: rr::plan_ao_passes' default), read at context creation
     DBuf ao_count, ao_rays;
     int64_t ao_pass = 0;
+    // one-bounce indirect light (rr_indirect_at_device, rr_render_indirect_device): one pass's gathered rays (48 bytes
+    // each) and colours (24); for the frames also the pass's camera rays (48 bytes per point; its first hits go to
+    // hitrec), the live list (4 bytes per ray) and the compaction's counts (one per 256 rays, then the live count and
+    // one per trace chunk); grown on demand.  The pass size RRAY_INDIRECT_PASS asks for in points (0:
+    // rr::plan_indirect_passes' default), read at context creation
+    DBuf ind_rays, ind_rgb, ind_cam, ind_list, ind_counts;
+    int64_t indirect_pass = 0;
     // the denoiser (rr_denoise_device): the guide records (32 bytes per pixel) and the two images the levels ping-pong
     // between (8 * channels bytes per pixel each; none for one iteration), grown on demand; dn_host: the device copies
     // of rr_denoise's host buffers
@@ -726,6 +733,10 @@ int run_levels(rr_ctx* c, const FrameFacts& facts, const rr::LevelArgs& base_arg
     if (rc == RR_OK && plan.order.ok) rc = refresh_order(c, base_args, plan, !facts.sw.no_tile_guess, st);
     if (rc != RR_OK) return rc;
     if (base0 != 0 && (!base_args.rays0 || base0 % 64 != 0 || aap)) return fail(RR_E_ARG, "internal: a starting base needs explicit rays and whole waves");
+    // an ordered batch whose live count is on the device (the indirect frames' live list): the kernels compare the count
+    // with the launch's own slots, so the list is one batch from slot 0
+    if (base_args.rays0 && base_args.list && base_args.n_dev && (plan.B < total || base0 != 0))
+        return fail(RR_E_ARG, "internal: a device-counted ordered batch is one batch");
     for (int64_t off = 0; off < total; off += plan.B) {
         const int64_t base = base0 + off, nb = std::min(plan.B, total - off);
         rr::LevelPlan short_batch;
@@ -861,6 +872,7 @@ int rr_create(int device, rr_ctx** out) {
     if (const char* b = std::getenv("RRAY_BATCH")) c->batch = std::max<int64_t>(1024, std::atoll(b));
     if (const char* b = std::getenv("RRAY_LENS_PASS")) c->lens_pass = std::max<int64_t>(0, std::atoll(b));
     if (const char* b = std::getenv("RRAY_AO_PASS")) c->ao_pass = std::max<int64_t>(0, std::atoll(b));
+    if (const char* b = std::getenv("RRAY_INDIRECT_PASS")) c->indirect_pass = std::max<int64_t>(0, std::atoll(b));
     if (const char* b = std::getenv("RRAY_DENOISE_LDS"))
         c->dn_lds_step = (int32_t)std::min<long long>(rr::RR_DN_LDS_MAX_STEP, std::max<long long>(0, std::atoll(b)));
     size_t free_b = 0, total_b = 0;
@@ -937,7 +949,7 @@ void rr_destroy(rr_ctx* c) {
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
                     &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb,
-                    &c->ao_count, &c->ao_rays, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host})
+                    &c->ao_count, &c->ao_rays, &c->ind_rays, &c->ind_rgb, &c->ind_cam, &c->ind_list, &c->ind_counts, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2674,6 +2686,243 @@ int rr_denoise(rr_ctx* c, const rr_denoise_desc* d, int64_t W, int64_t H, int32_
     HIPCHK(hipMemcpyAsync(out, base, bytes[0], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return RR_OK;
+}
+
+// ---- one-bounce indirect light (render_indirect.inc, ao_dir.hpp) ----
+// K gathered rays per point from indirect_rays_kernel, traced by the colour families' rays0 path a pass of whole points
+// at a time and averaged per point by indirect_resolve_kernel: the lens frames' structure with the occlusion frames'
+// points.  The frames trace only the rays of the samples that hit, through the listed kernels' ordered source with the
+// live count left on the device.  The isolation rule of the ray queries holds: counters in buffer 2, no frame state
+// touched.
+static_assert(sizeof(rr_indirect) == 16, "rr_indirect is 16 bytes (rray.h)");
+
+// what every indirect entry refuses of the parameters; fills the kernel's argument
+static int indirect_check(const rr_indirect* ind, rr::DevIndirect* P) {
+    if (!ind) return fail(RR_E_ARG, "indirect light: null rr_indirect");
+    if (ind->samples < 1 || ind->samples > RR_MAX_INDIRECT_SAMPLES)
+        return fail(RR_E_ARG, "indirect samples must be in 1.." + std::to_string(RR_MAX_INDIRECT_SAMPLES));
+    if (ind->remaining < 0 || ind->remaining > RR_MAX_DEPTH) return fail(RR_E_LIMIT, "rr_indirect.remaining out of range");
+    P->seed = ind->seed;
+    P->samples = (uint32_t)ind->samples;
+    P->pad = 0;
+    return RR_OK;
+}
+
+// rr_color_at_device's level 0: sample j's jitter identity is (j, path 1)
+static rr::LevelArgs indirect_level0(uint64_t seed, int32_t jitter_mode) {
+    rr::LevelArgs A{};
+    A.hs = 1;
+    A.aa = 1;
+    A.part = 0;
+    A.nparts = 1;
+    A.block_rows = 1;
+    A.seed = seed;
+    A.jitter_mode = jitter_mode;
+    return A;
+}
+// A pass's scratch seen from the frame's ray indices: the kernels index rays, sample identities and output slots by the
+// global j, so the pointers are biased by -r0 entries and never dereferenced outside the pass (integer arithmetic: the
+// biased addresses may lie below the allocations), as rr_render_lens_device does.
+static double* biased(double* p, int64_t r0, int per_ray) {
+    return reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(p) - (uintptr_t)r0 * per_ray * sizeof(double));
+}
+
+int rr_indirect_at_device(rr_ctx* c, int64_t n, const void* d_points, const void* d_normals, const rr_indirect* ind,
+                          uint64_t seed, int32_t jitter_mode, void* d_out, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevIndirect P{};
+    int rc = indirect_check(ind, &P);
+    if (rc != RR_OK) return rc;
+    rc = rays_check(c, n, !d_points || !d_normals || !d_out);
+    if (rc != RR_OK) return rc;
+    const int64_t K = ind->samples;
+    if (n * K >= ((int64_t)1 << 32)) return fail(RR_E_LIMIT, "an indirect batch must hold fewer than 2^32 rays (n * samples)");
+    if (n == 0) return RR_OK;
+    const rr::IndirectPassPlan plan = rr::plan_indirect_passes(n, ind->samples, c->batch, c->indirect_pass);
+    const int64_t pass_rays = std::min(plan.points, n) * K;
+    const FrameFacts facts = frame_facts(c, ind->remaining);
+    HIPCHK(hipSetDevice(c->device));
+    // one pass's rays and colours (grown on demand, as the lens frames')
+    HIPCHK(c->ind_rays.ensure((size_t)pass_rays * 6 * sizeof(double)));
+    HIPCHK(c->ind_rgb.ensure((size_t)pass_rays * 3 * sizeof(double)));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    const int saved_epoch = c->epoch;
+    c->epoch = 2;  // the query buffer (frame buffers keep their state), zeroed once per call
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));
+    rr::LevelArgs A = indirect_level0(seed, jitter_mode);
+    double* const rays = c->ind_rays.as<double>();
+    double* const rgb = c->ind_rgb.as<double>();
+    for (int64_t first = 0; first < n && rc == RR_OK; first += plan.points) {
+        const int64_t np = std::min(plan.points, n - first), r0 = first * K;  // r0 is a multiple of 64
+        const rr::AoPoints I{static_cast<const double*>(d_points) + 3 * first, static_cast<const double*>(d_normals) + 3 * first,
+                             3, 1, nullptr, first};
+        hipError_t e = rr::launch_indirect_rays(P, I, np, rays, nullptr, nullptr, nullptr, 0, st);
+        if (e != hipSuccess) {
+            rc = fail(RR_E_HIP, std::string("launch_indirect_rays: ") + hipGetErrorString(e));
+            break;
+        }
+        A.rays0 = biased(rays, r0, 6);
+        rc = run_levels(c, facts, A, np * K, ind->remaining, biased(rgb, r0, 3), st, nullptr, 0, 0, nullptr, r0);
+        if (rc != RR_OK) break;
+        e = rr::launch_indirect_resolve(rgb, nullptr, ind->samples, np, static_cast<double*>(d_out) + 3 * first, st);
+        if (e != hipSuccess) rc = fail(RR_E_HIP, std::string("launch_indirect_resolve: ") + hipGetErrorString(e));
+    }
+    c->epoch = saved_epoch;
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, n);
+    return RR_OK;
+}
+
+// what both frame entries refuse before they look at the context
+static int indirect_frame_check(const rr_camera* cam, const rr_render_opts* o, const rr_indirect* ind, const void* out,
+                                rr::DevIndirect* P) {
+    if (!cam || !o || !out) return fail(RR_E_ARG, "rr_render_indirect: null argument");
+    return indirect_check(ind, P);
+}
+static int indirect_ctx_check(const rr_ctx* c) {
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "indirect frames need a single-device context (no multi-device or virtual context)");
+    if (!c->has_scene) return fail(RR_E_ARG, "no scene uploaded");
+    return RR_OK;
+}
+
+int rr_render_indirect_device(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_indirect* ind, void* d_out,
+                              void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevIndirect P{};
+    int rc = indirect_frame_check(cam, o, ind, d_out, &P);
+    if (rc != RR_OK) return rc;
+    rc = indirect_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    rr_render_opts opts = *o;
+    opts.max_depth = 0;  // ignored here, as flags: the gathered rays' budget is rr_indirect.remaining
+    rc = check_opts(cam, &opts);
+    if (rc != RR_OK) return rc;
+    if (o->part != 0 || o->nparts != 1 || o->row_begin != 0 || o->row_end != 0)
+        return fail(RR_E_ARG, "indirect frames are whole frames: part 0 of 1, no band");
+    const int64_t total = cam->hsize * cam->vsize, K = ind->samples;
+    if (total >= ((int64_t)1 << 32) || total * K >= ((int64_t)1 << 32))
+        return fail(RR_E_LIMIT, "an indirect frame's rays (hsize * vsize * samples) must number fewer than 2^32");
+    const rr::IndirectPassPlan plan = rr::plan_indirect_passes(total, ind->samples, c->batch, c->indirect_pass);
+    const int64_t pass = std::min(plan.points, total), pass_rays = pass * K;
+    const FrameFacts facts = frame_facts(c, ind->remaining);
+    HIPCHK(hipSetDevice(c->device));
+    // one pass's camera rays, first-hit planes (RR_HIT_DOUBLES double planes, then the two int planes), gathered rays,
+    // colours and live list
+    const size_t d_bytes = (size_t)pass * rr::RR_HIT_DOUBLES * sizeof(double);
+    HIPCHK(c->ind_cam.ensure((size_t)pass * 6 * sizeof(double)));
+    HIPCHK(c->hitrec.ensure(d_bytes + (size_t)pass * 2 * sizeof(int32_t)));
+    HIPCHK(c->ind_rays.ensure((size_t)pass_rays * 6 * sizeof(double)));
+    HIPCHK(c->ind_rgb.ensure((size_t)pass_rays * 3 * sizeof(double)));
+    HIPCHK(c->ind_list.ensure((size_t)pass_rays * sizeof(uint32_t)));
+    double* const rays = c->ind_rays.as<double>();
+    double* const rgb = c->ind_rgb.as<double>();
+    uint32_t* const list = c->ind_list.as<uint32_t>();
+    // The trace of a pass: the live list in chunks of one run_levels batch each (one chunk unless RRAY_BATCH or the queue
+    // budget says otherwise), every chunk launched for its capacity with its live count on the device.  Planned before
+    // anything is enqueued: the per-level paths refuse here.
+    rr::LevelArgs A = indirect_level0(o->seed, o->jitter_mode);
+    A.rays0 = rays;
+    A.list = list;
+    const rr::FramePlan fp = plan_run(c, facts, A, pass_rays, ind->remaining, FrameOut{rgb, nullptr, 0, 0, nullptr});
+    if (fp.err != RR_OK) return fail(fp.err, fp.msg);
+    const int64_t chunk = std::min(pass_rays, fp.B), n_chunks = (pass_rays + chunk - 1) / chunk;
+    const int64_t n_blocks = (pass_rays + 255) / 256;
+    HIPCHK(c->ind_counts.ensure((size_t)(n_blocks + 1 + n_chunks) * sizeof(uint32_t)));
+    uint32_t* const block_count = c->ind_counts.as<uint32_t>();
+    uint32_t* const counts = block_count + n_blocks;
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    c->frame_timed = true;
+    HIPCHK(hipEventRecord(c->e0, st));
+    const int saved_epoch = c->epoch;
+    c->epoch = 2;  // the query buffer (frame buffers keep their state), zeroed once per frame
+    HIPCHK(hipMemsetAsync(frame_counters(c, 2), 0, kCounterBytes, st));
+    rr::HitOut O{};
+    O.node_object = c->node_object.as<int32_t>();
+    O.rec_d = c->hitrec.as<double>();
+    O.rec_i = reinterpret_cast<int32_t*>(c->hitrec.as<char>() + d_bytes);
+    O.stride = pass;
+    rr::LevelArgs C{};
+    set_camera(C, cam);  // the frames' DevCamera and affine flag
+    rr::LevelArgs H{};   // rr_hit_at_device's level 0 on the pass's camera rays
+    H.hs = 1;
+    H.aa = 1;
+    H.part = 0;
+    H.nparts = 1;
+    H.block_rows = 1;
+    H.nseg = H.nseg_out = 1;
+    H.counters = frame_counters(c, 2);
+    H.base = 0;
+    H.rays0 = c->ind_cam.as<double>();
+    // over_point and normalv are planes 12..14 and 9..11 of the records (HitOut.rec_d), object the first int plane
+    const rr::AoPoints planes{O.rec_d + 12 * pass, O.rec_d + 9 * pass, 1, pass, O.rec_i, 0};
+    for (int64_t first = 0; first < total && rc == RR_OK; first += plan.points) {
+        const int64_t np = std::min(plan.points, total - first), r0 = first * K;
+        hipError_t e = rr::launch_camera_rays_window(C.cam, C.cam_affine != 0, first, np, c->ind_cam.as<double>(), st);
+        if (e == hipSuccess) {
+            H.n = np;
+            set_level0_index(H);
+            e = rr::launch_hit(c->S, H, O, st);
+        }
+        if (e == hipSuccess) {
+            rr::AoPoints I = planes;
+            I.first = first;
+            e = rr::launch_indirect_rays(P, I, np, rays, list, block_count, counts, chunk, st);
+        }
+        if (e != hipSuccess) {
+            rc = fail(RR_E_HIP, std::string("indirect pass: ") + hipGetErrorString(e));
+            break;
+        }
+        A.rays0 = biased(rays, r0, 6);
+        for (int64_t b = 0; b * chunk < np * K && rc == RR_OK; ++b) {
+            A.list = list + b * chunk;
+            A.n_dev = counts + 1 + b;
+            rc = run_levels(c, facts, A, std::min(chunk, np * K - b * chunk), ind->remaining, biased(rgb, r0, 3), st);
+        }
+        if (rc != RR_OK) break;
+        e = rr::launch_indirect_resolve(rgb, O.rec_i, ind->samples, np, static_cast<double*>(d_out) + 3 * first, st);
+        if (e != hipSuccess) rc = fail(RR_E_HIP, std::string("launch_indirect_resolve: ") + hipGetErrorString(e));
+    }
+    c->epoch = saved_epoch;
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipEventRecord(c->e1, st));
+    HIPCHK(claim.release());
+    rays_stats_pending(c, total);
+    return RR_OK;
+}
+
+int rr_render_indirect(rr_ctx* c, const rr_camera* cam, const rr_render_opts* o, const rr_indirect* ind, double* out,
+                       rr_stats* stats) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    rr::DevIndirect P{};
+    int rc = indirect_frame_check(cam, o, ind, out, &P);
+    if (rc != RR_OK) return rc;
+    rc = indirect_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    if (cam->hsize <= 0 || cam->vsize <= 0 || cam->hsize > (1ll << 31) || cam->vsize > (1ll << 31))
+        return fail(RR_E_ARG, "bad camera size");
+    if (cam->hsize * cam->vsize >= ((int64_t)1 << 32) || cam->hsize * cam->vsize * ind->samples >= ((int64_t)1 << 32))
+        return fail(RR_E_LIMIT, "an indirect frame's rays (hsize * vsize * samples) must number fewer than 2^32");
+    const size_t img = (size_t)cam->hsize * (size_t)cam->vsize * 3 * sizeof(double);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->qout.ensure(img));
+    rc = rr_render_indirect_device(c, cam, o, ind, c->qout.p, nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, c->qout.p, img, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rr_stats local;
+    rc = rr_last_stats(c, stats ? stats : &local);
+    if (rc != RR_OK) return rc;
+    const uint64_t nan = (stats ? stats : &local)->nan_rays;
+    return nan ? nan_fail(nan) : RR_OK;
 }
 
 }  // extern "C"

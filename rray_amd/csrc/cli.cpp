@@ -16,6 +16,12 @@
 // camera; --denoise-color <sigma> adds the colour term, the other sigmas are the library's defaults 0.25 / 0.05 / 0.1):
 // with --samples the lens frame's colour image, with --ao-samples the <PREFIX>_ao.png plane.  Not with -a other than 1
 // or --adaptive.
+// --indirect <K> [--indirect-depth <D>] [--indirect-seed <N>] adds one bounce of indirect light to the PNG: the colour
+// frame plus (albedo * the hit object's diffuse) * rr_render_indirect's plane (K gathered rays per pixel, each traced
+// with `remaining` D, default 1; directions seeded with N, default 0) where the pixel's first ray hits, composed on the
+// host in plain f64 (rray_amd.indirect_compose); with --aov also <PREFIX>_indirect.png, the plane as composed.  With
+// --denoise the plane is filtered first, guided by the aa 1 first-hit planes.  One device; not with -a other than 1,
+// --adaptive or --samples.
 // No CPU fallback.
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +51,10 @@ static int usage(const char* msg) {
                  "      --aperture <A>     Lens frame: lens radius in camera space, 0 is a pinhole [default: 0]\n"
                  "      --focus <F>        Lens frame: camera-space distance of the plane in focus [default: 1]\n"
                  "      --pixel-jitter     Lens frame: each sample through a point uniform in its pixel\n"
-                 "      --denoise <I>      With --samples or --ao-samples: filter the lens frame / the _ao.png plane, I levels (1..8)\n"
+                 "      --indirect <K>     Add one bounce of indirect light, K gathered rays per pixel (1..1024); with --aov also <PREFIX>_indirect.png\n"
+                 "      --indirect-depth <D>  With --indirect: the gathered rays' reflection / refraction budget (0..8) [default: 1]\n"
+                 "      --indirect-seed <N>   With --indirect: seed of the gathered directions [default: 0]\n"
+                 "      --denoise <I>      With --samples, --ao-samples or --indirect: filter the lens frame / the _ao.png plane / the indirect plane, I levels (1..8)\n"
                  "      --denoise-color <SIGMA>  With --denoise: switch the colour term on (>= 0) [default: 0]\n"
                  "  -h, --help             Print help\n  -V, --version          Print version\n");
     return 2;
@@ -218,6 +227,73 @@ static int render_lens(const std::string& scene, long long width, long long heig
     return rc;
 }
 
+// --indirect: the colour frame (camera.rs:113's depth 5 and seed 0, as the plain path) plus one bounce: per pixel
+// base + (albedo * diffuse[object]) * indirect where object >= 0, base elsewhere, plain f64 in that order
+// (rray_amd.indirect_compose).  dn (--denoise; or null): the indirect plane goes through rr_denoise with the aa 1
+// first-hit planes before it is composed.  prefix (--aov; or empty): also <PREFIX>_indirect.png, the plane as composed.
+static int render_indirect(const std::string& scene, long long width, long long height, int device, const rr_indirect& ind,
+                           const rr_denoise_desc* dn, const std::string& output, const std::string& prefix) {
+    std::ifstream f(scene, std::ios::binary);
+    if (!f) {  // scene_builder_yaml.rs:434 panics "File does not exist"
+        std::fprintf(stderr, "rray: File does not exist (code %d)\n", RR_E_IO);
+        return RR_E_IO;
+    }
+    std::stringstream ss;
+    ss << f.rdbuf();
+    rr_scene* S = nullptr;
+    rr_camera cam;
+    int rc = rr_scene_from_yaml(ss.str().c_str(), nullptr, width, height, 1, &S, &cam);
+    rr_ctx* ctx = nullptr;
+    if (rc == RR_OK) rc = rr_create(device, &ctx);
+    if (rc == RR_OK) rc = rr_scene_upload(ctx, rr_scene_desc_of(S));
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<double> avg(n * 3), plane(n * 3), depth(n), normal(n * 3), albedo(n * 3);
+    std::vector<int32_t> object(n);
+    if (rc == RR_OK) {
+        rr_render_opts o{};
+        o.aa = 1;
+        o.max_depth = 5;
+        o.nparts = 1;
+        o.block_rows = 8;
+        o.flags = RR_OUT_AVG;
+        rc = rr_render(ctx, &cam, &o, nullptr, avg.data(), nullptr);
+        o.flags = 0;
+        if (rc == RR_OK)
+            rc = rr_render_aov(ctx, &cam, &o, RR_AOV_DEPTH | RR_AOV_NORMAL | RR_AOV_OBJECT | RR_AOV_ALBEDO, depth.data(),
+                               normal.data(), object.data(), albedo.data(), nullptr);
+        if (rc == RR_OK) rc = rr_render_indirect(ctx, &cam, &o, &ind, plane.data(), nullptr);
+        if (rc == RR_OK && dn) {
+            std::vector<double> raw = plane;
+            rc = rr_denoise(ctx, dn, width, height, 3, raw.data(), depth.data(), normal.data(), object.data(),
+                            albedo.data(), plane.data());
+        }
+    }
+    if (rc == RR_OK) {
+        const rr_scene_desc* d = rr_scene_desc_of(S);
+        for (size_t i = 0; i < n; ++i) {
+            if (object[i] < 0) continue;
+            const double kd = d->mat[7 * (size_t)d->material[object[i]] + 1];
+            for (int c = 0; c < 3; ++c) {
+                const double w = albedo[3 * i + c] * kd;
+                avg[3 * i + c] = avg[3 * i + c] + w * plane[3 * i + c];
+            }
+        }
+        std::vector<uint8_t> rgba(n * 4);
+        rr_quantize(avg.data(), (int64_t)n, rgba.data());
+        rc = rr_write_png(output.c_str(), rgba.data(), width, height);
+        if (rc == RR_OK && !prefix.empty()) {
+            rr_quantize(plane.data(), (int64_t)n, rgba.data());
+            rc = rr_write_png((prefix + "_indirect.png").c_str(), rgba.data(), width, height);
+        }
+        if (rc != RR_OK) std::fprintf(stderr, "rray: cannot write PNG (code %d)\n", rc);
+    } else {
+        std::fprintf(stderr, "rray: --indirect: %s (code %d)\n", rr_last_error(), rc);
+    }
+    rr_destroy(ctx);
+    rr_scene_free(S);
+    return rc;
+}
+
 static bool parse_double(const char* v, double& out) {
     char* end = nullptr;
     out = std::strtod(v, &end);
@@ -239,6 +315,9 @@ int main(int argc, char** argv) {
     dn.sigma_depth = 0.05;
     dn.sigma_albedo = 0.1;
     bool denoise = false, denoise_color = false;
+    rr_indirect ind{};
+    ind.remaining = 1;
+    bool indirect = false, indirect_depth = false, indirect_seed = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&](const char* name) -> const char* {
@@ -281,6 +360,24 @@ int main(int argc, char** argv) {
             if (!parse_double(val("--denoise-color"), dn.sigma_color) || dn.sigma_color < 0.0)
                 return usage("--denoise-color needs a number >= 0 (the colour sigma)");
             denoise_color = true;
+        } else if (a == "--indirect") {
+            long long K = 0;
+            if (!parse_usize(val("--indirect"), K) || K < 1 || K > RR_MAX_INDIRECT_SAMPLES)
+                return usage("--indirect needs a number from 1 to 1024");
+            ind.samples = (int32_t)K;
+            indirect = true;
+        } else if (a == "--indirect-depth") {
+            long long D = 0;
+            if (!parse_usize(val("--indirect-depth"), D) || D > RR_MAX_DEPTH)
+                return usage("--indirect-depth needs a number from 0 to 8");
+            ind.remaining = (int32_t)D;
+            indirect_depth = true;
+        } else if (a == "--indirect-seed") {
+            const char* v = val("--indirect-seed");
+            long long N = 0;
+            if (!parse_usize(v, N) || std::strlen(v) > 18) return usage("--indirect-seed needs a number (at most 18 digits)");
+            ind.seed = (uint64_t)N;
+            indirect_seed = true;
         } else if (a == "--adaptive") {
             const char* v = val("--adaptive");
             char* end = nullptr;
@@ -318,8 +415,12 @@ int main(int argc, char** argv) {
     if (denoise_color && !denoise) return usage("--denoise-color is valid only with --denoise <I>");
     if (denoise && (aa != 1 || adaptive))
         return usage("--denoise cannot be combined with -a other than 1 or with --adaptive");
-    if (denoise && !lens_frame && !ao_samples)
-        return usage("--denoise filters a lens frame (--samples) or an occlusion plane (--ao-samples): give one of them");
+    if ((indirect_depth || indirect_seed) && !indirect)
+        return usage("--indirect-depth and --indirect-seed are valid only with --indirect <K>");
+    if (indirect && (aa != 1 || adaptive || lens_frame))
+        return usage("--indirect cannot be combined with -a other than 1, --adaptive or --samples (a lens frame)");
+    if (denoise && !lens_frame && !ao_samples && !indirect)
+        return usage("--denoise filters a lens frame (--samples), an occlusion plane (--ao-samples) or the indirect plane (--indirect): give one of them");
     if (lens_frame && (aa != 1 || adaptive || !aov.empty()))
         return usage("--samples, --aperture, --focus and --pixel-jitter cannot be combined with -a other than 1, --adaptive or --aov");
     std::vector<int> devices;
@@ -349,6 +450,9 @@ int main(int argc, char** argv) {
     if (lens_frame) {
         if (devices.size() != 1) return usage("a lens frame renders on one device");
         if (render_lens(scene, width, height, devices[0], lens, denoise ? &dn : nullptr, output) != RR_OK) return 1;
+    } else if (indirect) {
+        if (devices.size() != 1) return usage("--indirect renders on one device");
+        if (render_indirect(scene, width, height, devices[0], ind, denoise ? &dn : nullptr, output, aov) != RR_OK) return 1;
     } else if (adaptive) {
         if (devices.size() != 1) return usage("--adaptive renders on one device");
         if (render_adaptive(scene, width, height, (int)aa, devices[0], threshold, output) != RR_OK) return 1;

@@ -242,6 +242,31 @@ inline AoPassPlan plan_ao_passes(int64_t n_points, int32_t samples, int64_t batc
     return p;
 }
 
+// The pass split of rr_indirect_at_device and rr_render_indirect_device (one-bounce indirect light):
+// passes of whole points, K gathered rays each, so that the scratch of a pass (48 + 24 bytes per ray) is bounded whatever
+// the batch or the frame.  plan_ao_passes' rules with RRAY_INDIRECT_PASS for `want`: every pass but the last holds
+// `points` points, a multiple of 64 (a pass's first ray is then a multiple of 64 too: whole waves); want > 0: that many
+// points rounded up to a multiple of 64; else the largest multiple of 64 with at most kRayPassMax rays, and at least 64
+// points.  Either is capped by the context's batch rounded down to a multiple of 64 (at least 64: a frame pass's first
+// hits are one launch of the first-hit kernel) and kept below 2^32 rays.  Pass k holds points
+// [k * points, min(n_points, (k + 1) * points)).
+struct IndirectPassPlan {
+    int64_t points;  // per pass (the last may be shorter)
+    int64_t passes;
+};
+inline IndirectPassPlan plan_indirect_passes(int64_t n_points, int32_t samples, int64_t batch, int64_t want) {
+    IndirectPassPlan p{};
+    if (n_points <= 0 || samples < 1 || batch <= 0) return p;
+    if (want > 0)
+        p.points = want > ((int64_t)1 << 40) ? (int64_t)1 << 40 : (want + 63) / 64 * 64;
+    else
+        p.points = std::max<int64_t>(64, kRayPassMax / samples / 64 * 64);
+    p.points = std::min<int64_t>(p.points, std::max<int64_t>(64, batch / 64 * 64));
+    p.points = std::min<int64_t>(p.points, std::max<int64_t>(64, ((((int64_t)1 << 32) - 1) / samples) / 64 * 64));
+    p.passes = (n_points + p.points - 1) / p.points;
+    return p;
+}
+
 struct FramePlan {
     Family family;
     bool fused, ext;  // segmented queues between the levels; refraction halves beside the pending sums

@@ -96,7 +96,9 @@ struct LevelArgs {
     // frame); n_dev holds the live event count (aa^2 x the listed pixels), the launch covers the capacity.  Last in
     // the struct, so that no other field moves in the kernels that never read them.
     // (with rays0, the rr::listed kernels read list as the order of an ordered ray batch instead, DESIGN.md §3.19: level-0
-    // slot base + i works on ray list[base + i], n_dev null and n the host's count)
+    // slot base + i works on ray list[base + i]; n_dev null and n the host's count, or — one batch, base 0, the indirect
+    // frames' live list — n the capacity, n_dev the live count the kernels' live_count reads, and every one of the n
+    // list slots a ray of the batch)
     const uint32_t* list;
     uint32_t list_w;
     // the flat fused level-0 kernels (shade_body.inc UH): the scalar path for hit-uniform tiles, planes' normals from
@@ -409,6 +411,26 @@ hipError_t launch_camera_rays_window(const DevCamera& cam, bool affine, int64_t 
                                      hipStream_t stream);
 // ao_resolve_kernel: out[i] = (double)(K - count[i]) / (double)K, i < n
 hipError_t launch_ao_resolve(const int32_t* count, int32_t samples, int64_t n, double* out, hipStream_t stream);
+
+// One-bounce indirect light (render_indirect.inc in render_rays.hip; the definition is rray.h's
+// RR_HAS_INDIRECT block).  The rr_indirect parameters as indirect_rays_kernel reads them (`remaining` is the trace's).
+struct DevIndirect {
+    uint64_t seed;
+    uint32_t samples, pad;  // K
+};
+// indirect_rays_kernel over n points in AoPoints' form (I.first: the hash index of point 0; (I.first + n) * K < 2^32):
+// ray (I.first + i) * K + k at rays + 6 * (i * K + k).  list null (the point query): every point is evaluated and
+// I.object is not read.  list non-null (the frames; I.object required): the pairs of a miss write no ray, and
+// list[0 .. live) holds the global indices (I.first + i) * K + k of the other pairs in increasing order and
+// list[live .. n * K) the pass's first ray index (slots a launch for the capacity may read but never trace); block_count
+// (one uint32 per 256 pairs) is scratch, counts[0] = live and counts[1 + b] = the live entries among list slots
+// [b * chunk, (b + 1) * chunk), b < ceil(n * K / chunk): all computed on the device, nothing waits.
+hipError_t launch_indirect_rays(const DevIndirect& P, const AoPoints& I, int64_t n, double* rays, uint32_t* list,
+                                uint32_t* block_count, uint32_t* counts, int64_t chunk, hipStream_t stream);
+// indirect_resolve_kernel: out[i] = (((c[i*K] + c[i*K + 1]) + ...) + c[i*K + K - 1]) / (double)K per channel, i < n;
+// object non-null: zeros where object[i] < 0, whose colours are not read
+hipError_t launch_indirect_resolve(const double* colours, const int32_t* object, int32_t samples, int64_t n, double* out,
+                                   hipStream_t stream);
 
 // The edge-avoiding denoiser (render_denoise.inc in render_rays.hip; the definition is rray.h's
 // RR_HAS_DENOISE block, its arithmetic denoise_tap.hpp's).

@@ -10,6 +10,8 @@
 //   render_ao.inc       the ambient-occlusion pairs and resolve kernels (rr_ao_at_device, rr_render_ao_device): the one
 //                       part of this unit that walks the scene, with shadow_query_kernel's shadowed<> instantiation
 //   render_denoise.inc  the edge-avoiding denoiser's pack and level kernels (rr_denoise_device), by denoise_tap.hpp
+//   render_indirect.inc the one-bounce indirect rays, their live list and the resolve step (rr_indirect_at_device,
+//                       rr_render_indirect_device)
 // None of the others reads the scene.  The queries' walks are the existing kernels' (hit_kernel's ray-batch instantiation, the
 // colour families with A.rays0, shadow_query_kernel), launched on the caller's buffers as they are.
 #include <algorithm>
@@ -119,6 +121,7 @@ __global__ void __launch_bounds__(256) hit_records_ordered_kernel(const int32_t*
 #include "render_order.inc"
 #include "render_lens.inc"
 #include "render_ao.inc"
+#include "render_indirect.inc"
 #include "render_denoise.inc"
 
 hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t st) {

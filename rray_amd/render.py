@@ -658,6 +658,37 @@ class Renderer:
         check(lib().rr_render_ao_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
 
     # ---- the edge-avoiding denoiser (rray.h RR_HAS_DENOISE) ----
+    # ---- one-bounce indirect light (rray.h RR_HAS_INDIRECT): what the surroundings send to a point ----
+    def indirect_at_device(self, n, d_points, d_normals, ind, d_out, seed=0, jitter_mode=0, stream=None):
+        """rr_indirect_at_device: the gathered radiance of n points — two n x 3 f64 device arrays, positions and unit
+        normals (ints: device pointers) — into d_out (n x 3 f64): indirect_resolve of color_at_device (remaining =
+        ind.remaining, this seed and jitter_mode) over indirect_rays(points, normals, ind).  Ordered on `stream` (int or
+        None), not synchronised; last_stats() afterwards is the colour trace's, with samples == n."""
+        d = ind.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_points, d_normals)]
+        q = [C.c_void_p(x) if x else None for x in (d_out, stream)]
+        check(lib().rr_indirect_at_device(self.h, n, *p, C.byref(d), seed & 0xFFFFFFFFFFFFFFFF, jitter_mode, *q))
+
+    def render_indirect(self, cam, ind, aa=1, seed=0, jitter_mode=0):
+        """rr_render_indirect: the gathered radiance of `cam`'s canvas samples -> dict(indirect=(vsize, hsize, 3) f64,
+        stats): one value per canvas sample, never averaged and not multiplied by the surface's albedo (indirect_compose
+        does that); indirect_at_device at over_point / normalv of hit_at_device over camera_rays_device(cam), (0, 0, 0)
+        where the sample misses — a miss traces nothing: stats['rays'] == the camera's rays + the rays of a color_at_device
+        over the hits' gathered rays only."""
+        o = _lib.RenderOpts(aa, 0, seed & 0xFFFFFFFFFFFFFFFF, jitter_mode, 0, 1, 8, 0, 0, 0)
+        d = ind.desc()
+        out = np.zeros((cam.vsize, cam.hsize, 3), np.float64)
+        st = _lib.Stats()
+        check(lib().rr_render_indirect(self.h, C.byref(cam), C.byref(o), C.byref(d), _dp(out), C.byref(st)))
+        return {"indirect": out, "stats": st.as_dict()}
+
+    def render_indirect_device(self, cam, opts, ind, d_out, stream=None):
+        """rr_render_indirect_device: the plane into d_out (int: a device pointer to vsize * hsize * 3 f64), ordered on
+        `stream` (int or None), not synchronised; NaN rays are counted in last_stats()['nan_rays'], never raised."""
+        d = ind.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_out, stream)]
+        check(lib().rr_render_indirect_device(self.h, C.byref(cam), C.byref(opts), C.byref(d), *p))
+
     def denoise(self, img, dn, depth=None, normal=None, object=None, albedo=None):
         """rr_denoise: `img` (H, W) or (H, W, 1) or (H, W, 3) f64 filtered on the device with the guide planes that are
         given (render_aov's layouts) -> an array of img's shape; denoise_filter of the same arguments, bit for bit."""
@@ -883,6 +914,67 @@ def ao_resolve(occluded, samples):
     K = int(samples)
     c = np.asarray(occluded).astype(np.int64).reshape(-1, K).sum(axis=1)
     return (K - c).astype(np.float64) / float(K)
+
+
+class Indirect:
+    """rr_indirect (rray.h RR_HAS_INDIRECT): `samples` gathered rays per point, cosine-weighted around the normal, each
+    traced with `remaining` further reflections / refractions; `seed` seeds their directions (ambient occlusion and the
+    lens frames draw from the same counters: give them different seeds)."""
+
+    def __init__(self, samples, remaining=1, seed=0):
+        self.samples, self.remaining, self.seed = int(samples), int(remaining), int(seed)
+
+    def desc(self):
+        return _lib.IndirectDesc(self.samples, self.remaining, self.seed & 0xFFFFFFFFFFFFFFFF)
+
+    def __repr__(self):
+        return f"Indirect(samples={self.samples}, remaining={self.remaining}, seed={self.seed})"
+
+
+def indirect_rays(points, normals, ind, first=0):
+    """The gathered rays in numpy (rray.h RR_HAS_INDIRECT), the kernel's definition and its tests' reference: points and
+    unit normals (n, 3) f64 -> (n * K, 6) f64 in camera_rays_device's layout; ray i * K + k is origin points[i] and
+    direction ao_directions(normals, ind, first)[i][k], taken as it is, for points first .. first + n - 1 (their hash
+    indices)."""
+    P = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    w = ao_directions(normals, ind, first)
+    K = int(ind.samples)
+    if len(w) != len(P):
+        raise ValueError("indirect_rays: as many normals as points")
+    out = np.empty((len(P), K, 6), np.float64)
+    out[:, :, 0:3] = P[:, None, :]
+    out[:, :, 3:6] = w
+    return out.reshape(-1, 6)
+
+
+def indirect_resolve(colours, samples):
+    """The gathered value in numpy: colours (n * K, 3) -> (n, 3), per channel (((L_0 + L_1) + ...) + L_{K-1}) / float(K),
+    summed in increasing k (lens_resolve's sum)."""
+    return lens_resolve(colours, samples)
+
+
+def object_diffuse(scene):
+    """material.diffuse of every object of a scene (a SceneBuilder or a YamlScene), read from scene.desc():
+    mat[material[id]][1], (n_objects,) f64 — what indirect_compose weighs the bounce with.  A group or a CSG node has
+    no material (material[id] < 0) and is never a sample's first hit: 0.0."""
+    d = scene.desc()
+    n = int(d.n_objects)
+    return np.array([d.mat[7 * d.material[i] + 1] if d.material[i] >= 0 else 0.0 for i in range(n)], np.float64)
+
+
+def indirect_compose(base, indirect, albedo, object, diffuse):
+    """A colour frame plus its bounce, per sample in plain f64 in this order: base + (albedo * diffuse[object]) * indirect
+    where object >= 0, base elsewhere.  base, indirect, albedo: (H, W, 3) f64 (render, render_indirect and render_aov's
+    albedo plane, or their filtered forms); object: (H, W) int32 (render_aov's object plane); diffuse: object_diffuse."""
+    base = np.asarray(base, np.float64)
+    ind = np.asarray(indirect, np.float64).reshape(base.shape)
+    alb = np.asarray(albedo, np.float64).reshape(base.shape)
+    obj = np.asarray(object).reshape(base.shape[:-1])
+    kd = np.asarray(diffuse, np.float64)
+    hit = obj >= 0
+    with np.errstate(all="ignore"):
+        w = alb * kd[np.where(hit, obj, 0)][..., None]
+        return np.where(hit[..., None], base + w * ind, base)
 
 
 class Denoise:
