@@ -711,6 +711,86 @@ int rr_render_indirect(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* 
 int rr_render_indirect_device(rr_ctx* ctx, const rr_camera* cam, const rr_render_opts* opts, const rr_indirect* ind,
                               void* d_out, void* hip_stream);
 
+/* ---- temporal accumulation: reproject a frame's history (additive to ABI 11; test RR_HAS_TEMPORAL) ----
+ * Blends a frame's image with the accumulated image of the previous frame of the same static scene, seen from another
+ * (or the same) camera: each pixel's first hit is projected into the previous camera, the history is gathered there
+ * bilinearly from the taps that show the same surface, and the two are blended by the history's length.  One
+ * image-space kernel; everything it reads is what rr_render_aov_device and the stochastic frames write.
+ * Frames: `cur` holds the current frame's image (`in`, H x W x C doubles, C in {1, 3}) and first-hit planes, `prev` the
+ * previous call's outputs (out as image, n_out as count, m2_out as m2) with the previous frame's planes.  Planes are
+ * H x W in rr_render_aov's layouts.  Outputs: out (H x W x C doubles), n_out (int32 history lengths), m2_out (H x W x C
+ * running second moments, or NULL together with prev.m2).  A history whose counts are all 0 is "no history": that is
+ * how the first frame is passed.
+ * Plain f64 in exactly the order written, no contraction; the only functions are sqrt, fabs and floor
+ * (rray_amd.temporal_filter is the same in numpy):
+ *   M = rr_camera_inverse(cam), M' = rr_camera_inverse(prev_cam), T' = prev_cam->transform
+ *   X_M(x, y, z)[r] = ((M[4r] * x + M[4r+1] * y) + M[4r+2] * z) + M[4r+3] * 1.0
+ *   ray(cam, x, y), the pinhole ray of the lens block above at the pixel centre: wx = half_width - ((double)x + 0.5) *
+ *     pixel_size, wy = half_height - ((double)y + 0.5) * pixel_size; o = X_M(0, 0, 0), f = X_M(wx, wy, -1), d = f - o,
+ *     mag = sqrt((dx * dx + dy * dy) + dz * dz), direction d / mag
+ *   void(p) in a frame: !(depth[p] < +inf), or that frame's object plane is given and its id < 0
+ * For pixel p = (x, y) with z = cur.depth[p]:
+ *   1. void(p): out = in, n_out = 1, m2_out[c] = in[c] * in[c]
+ *   2. world point: (o, d) = ray(cam, x, y); P[r] = o[r] + z * d[r]
+ *   3. static cameras (every field of the two rr_camera compares ==, so a NaN anywhere makes them unequal): the only
+ *      candidate tap is q = p with w = 1.0, and te = z: progressive accumulation under a fixed camera is exact
+ *   4. moving cameras: c[r] = ((T'[4r] * Px + T'[4r+1] * Py) + T'[4r+2] * Pz) + T'[4r+3] * 1.0; no candidate if
+ *      !(c[2] < 0.0); m = -c[2]; sx = c[0] / m; sy = c[1] / m; fx = (half_width' - sx) / pixel_size' - 0.5;
+ *      fy = (half_height' - sy) / pixel_size' - 0.5; no candidate if !(fx > -1.0 && fx < W && fy > -1.0 && fy < H);
+ *      x0 = floor(fx), ax = fx - x0, y0 = floor(fy), ay = fy - y0; candidates for j = 0..1 (outer), i = 0..1 (inner):
+ *      q = (x0 + i, y0 + j), w = (i ? ax : 1.0 - ax) * (j ? ay : 1.0 - ay); o' = X_M'(0, 0, 0), e = P - o',
+ *      te = sqrt((e0 * e0 + e1 * e1) + e2 * e2)
+ *   5. a candidate is skipped when any of these holds, tested in this order (each written so that a NaN skips it):
+ *      q outside the frame; void(q) in the previous planes; prev.count[q] < 1; RR_TP_OBJECT and the ids differ;
+ *      sigma_normal > 0 and !(1.0 - ((nx_p * nx_q + ny_p * ny_q) + nz_p * nz_q) <= sigma_normal);
+ *      sigma_plane > 0 and, with (o', d_q) = ray(prev_cam, q), Q[r] = o'[r] + z_q * d_q[r],
+ *      g = (n0 * (Q0 - P0) + n1 * (Q1 - P1)) + n2 * (Q2 - P2) over the current normal n: !(fabs(g) <= sigma_plane * te)
+ *      (the tap must lie on the current pixel's tangent plane: a floor seen at a glancing angle keeps its history,
+ *      which no relative depth tolerance allows); !(w > 0.0)
+ *   6. for each surviving tap: acc[c] = acc[c] + w * prev.image[q][c] (accm2 likewise over prev.m2); ws = ws + w;
+ *      nmin = min(nmin, prev.count[q])
+ *   7. if any tap survived: h[c] = acc[c] / ws, hm2[c] = accm2[c] / ws; n = min(nmin + 1, max_history);
+ *      a = 1.0 / (double)n; if a < alpha then a = alpha; out[c] = h[c] + (in[c] - h[c]) * a;
+ *      m2_out[c] = hm2[c] + (in[c] * in[c] - hm2[c]) * a; n_out = n.  Otherwise as for a void pixel.
+ * RR_E_ARG: a null desc, camera, frame, out or n_out; C not 1 or 3; W or H < 1; either camera's hsize / vsize not W / H;
+ * a missing image, depth or previous count plane (cur.count and cur.m2 are ignored); sigma_plane > 0 without cur.normal,
+ * sigma_normal > 0 without both normal planes, RR_TP_OBJECT without both object planes; m2_out without prev.m2 or
+ * prev.m2 without m2_out; max_history outside 1..RR_MAX_TEMPORAL_HISTORY; alpha outside 0..1 or a sigma negative or
+ * not finite; unknown flag bits; an output overlapping an input or another output; a multi-device or virtual context.
+ * RR_E_LIMIT: W * H >= 2^31.  A camera whose inverse rr_camera_inverse refuses returns that code.  No scene is needed.
+ * rr_temporal_reference: host only, no context: the definition, by the very function the kernel calls.
+ * rr_temporal: host buffers, runs on the device, blocking.
+ * rr_temporal_device: device buffers on the context's device, enqueued on `hip_stream` (NULL: ctx stream) and NOT
+ *   synchronised; the stream claim and device guard of the other _device entries; one kernel launch, no scratch.  Frame
+ *   state and rr_last_stats are left alone, as by rr_denoise_device. */
+#define RR_HAS_TEMPORAL 1
+#define RR_TP_OBJECT 1 /* a tap on another object id is skipped */
+#define RR_MAX_TEMPORAL_HISTORY 1048576
+typedef struct {
+    int32_t flags;       /* RR_TP_OBJECT or 0; other bits: RR_E_ARG */
+    int32_t max_history; /* 1..RR_MAX_TEMPORAL_HISTORY: n_out never exceeds it */
+    double alpha;        /* 0..1: floor of the blend factor (0: a running mean up to max_history) */
+    double sigma_plane;  /* >= 0, finite; 0 switches the term off; needs the current normal plane */
+    double sigma_normal; /* >= 0, finite; 0 switches the term off; needs both normal planes */
+} rr_temporal_desc;      /* 32 bytes */
+typedef struct {         /* one frame's planes, H x W, rr_render_aov's layouts; host or device pointers by entry */
+    const void* image;   /* H x W x C doubles: `in` for the current frame, the accumulated `out` of the previous one */
+    const void* depth;   /* doubles, +inf: miss.  Required */
+    const void* normal;  /* H x W x 3 doubles or NULL */
+    const void* object;  /* int32 or NULL */
+    const void* count;   /* previous frame only: int32 history lengths (its n_out); NULL in the current frame */
+    const void* m2;      /* previous frame only: H x W x C second moments (its m2_out) or NULL */
+} rr_temporal_frame;     /* 48 bytes */
+int rr_temporal_reference(const rr_temporal_desc* desc, int64_t width, int64_t height, int32_t channels,
+                          const rr_camera* cam, const rr_temporal_frame* cur, const rr_camera* prev_cam,
+                          const rr_temporal_frame* prev, double* out, int32_t* n_out, double* m2_out);
+int rr_temporal(rr_ctx* ctx, const rr_temporal_desc* desc, int64_t width, int64_t height, int32_t channels,
+                const rr_camera* cam, const rr_temporal_frame* cur, const rr_camera* prev_cam,
+                const rr_temporal_frame* prev, double* out, int32_t* n_out, double* m2_out);
+int rr_temporal_device(rr_ctx* ctx, const rr_temporal_desc* desc, int64_t width, int64_t height, int32_t channels,
+                       const rr_camera* cam, const rr_temporal_frame* cur, const rr_camera* prev_cam,
+                       const rr_temporal_frame* prev, void* d_out, void* d_n_out, void* d_m2_out, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

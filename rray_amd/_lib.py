@@ -86,7 +86,7 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
            "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device",
            "rr_denoise_reference", "rr_denoise", "rr_denoise_device", "rr_indirect_at_device", "rr_render_indirect",
-           "rr_render_indirect_device"]
+           "rr_render_indirect_device", "rr_temporal_reference", "rr_temporal", "rr_temporal_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -135,6 +135,22 @@ RR_MAX_INDIRECT_SAMPLES = 1024
 class IndirectDesc(C.Structure):
     """rr_indirect (RR_HAS_INDIRECT): gathered rays per point, their `remaining`, the directions' seed."""
     _fields_ = [("samples", C.c_int32), ("remaining", C.c_int32), ("seed", C.c_uint64)]
+
+
+RR_TP_OBJECT = 1
+RR_MAX_TEMPORAL_HISTORY = 1048576
+
+
+class TemporalDesc(C.Structure):
+    """rr_temporal_desc (RR_HAS_TEMPORAL): flags, the history cap, the blend floor and the two sigmas (0: term off)."""
+    _fields_ = [("flags", C.c_int32), ("max_history", C.c_int32), ("alpha", C.c_double), ("sigma_plane", C.c_double),
+                ("sigma_normal", C.c_double)]
+
+
+class TemporalFrame(C.Structure):
+    """rr_temporal_frame (RR_HAS_TEMPORAL): one frame's planes, host or device pointers by entry."""
+    _fields_ = [("image", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("object", C.c_void_p),
+                ("count", C.c_void_p), ("m2", C.c_void_p)]
 
 
 def hit_dtype():
@@ -253,6 +269,12 @@ def lib():
     L.rr_denoise_reference.argtypes = [C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
     L.rr_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _I, _D, _D]
     L.rr_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseDesc), C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 7
+    # temporal accumulation (RR_HAS_TEMPORAL)
+    _tp = [C.POINTER(TemporalDesc), C.c_int64, C.c_int64, C.c_int32, C.POINTER(Camera), C.POINTER(TemporalFrame),
+           C.POINTER(Camera), C.POINTER(TemporalFrame)]
+    L.rr_temporal_reference.argtypes = _tp + [C.c_void_p] * 3
+    L.rr_temporal.argtypes = [C.c_void_p] + _tp + [C.c_void_p] * 3
+    L.rr_temporal_device.argtypes = [C.c_void_p] + _tp + [C.c_void_p] * 4
     # one-bounce indirect light (RR_HAS_INDIRECT)
     L.rr_indirect_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(IndirectDesc),
                                         C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]

@@ -18,6 +18,7 @@
 #include "flatten.hpp"
 #include "ao_dir.hpp"
 #include "denoise_tap.hpp"
+#include "temporal_tap.hpp"
 #include "frame_plan.hpp"
 #include "kernels.hpp"
 #include "multi.hpp"
@@ -113,6 +114,11 @@ struct rr_ctx {
     // measured choice (DESIGN.md §3.22's A/B): 2 for one channel, 1 for three.  RRAY_DENOISE_LDS=<0..2> overrides (0: every
     // level direct), read at context creation
     int32_t dn_lds_step = -1;
+    // temporal accumulation (rr_temporal_device needs no scratch): tp_host holds the device copies of rr_temporal's host
+    // buffers.  tp_rows: the kernel's lane map, 0 the 32 x 8 tile, 1 row-major (DESIGN.md §3.24's A/B);
+    // RRAY_TEMPORAL_ROWS=<0|1> overrides the default, read at context creation
+    DBuf tp_host;
+    int32_t tp_rows = 0;
     // adaptive frames (rr_render_adaptive_device): per-pixel flags, per-block counts / offsets, the totals
     // {refined pixels, refine-pass events} and the list of refined pixels; the refine pass's samples go to `canvas`
     DBuf adapt_flags, adapt_blocks, adapt_counts, adapt_list, adapt_mask;
@@ -875,6 +881,7 @@ int rr_create(int device, rr_ctx** out) {
     if (const char* b = std::getenv("RRAY_INDIRECT_PASS")) c->indirect_pass = std::max<int64_t>(0, std::atoll(b));
     if (const char* b = std::getenv("RRAY_DENOISE_LDS"))
         c->dn_lds_step = (int32_t)std::min<long long>(rr::RR_DN_LDS_MAX_STEP, std::max<long long>(0, std::atoll(b)));
+    if (const char* b = std::getenv("RRAY_TEMPORAL_ROWS")) c->tp_rows = std::atoll(b) != 0 ? 1 : 0;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) c->queue_budget = free_b / 2;
     if (const char* q = std::getenv("RRAY_QUEUE_BUDGET_MB")) c->queue_budget = (size_t)std::max(1ll, std::atoll(q)) << 20;
@@ -949,7 +956,8 @@ void rr_destroy(rr_ctx* c) {
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
                     &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb,
-                    &c->ao_count, &c->ao_rays, &c->ind_rays, &c->ind_rgb, &c->ind_cam, &c->ind_list, &c->ind_counts, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host})
+                    &c->ao_count, &c->ao_rays, &c->ind_rays, &c->ind_rgb, &c->ind_cam, &c->ind_list, &c->ind_counts, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host,
+                    &c->tp_host})
         b->release();
     for (auto& b : c->comb) b.release();
     for (auto& b : c->comb_ext) b.release();
@@ -2684,6 +2692,179 @@ int rr_denoise(rr_ctx* c, const rr_denoise_desc* d, int64_t W, int64_t H, int32_
     rc = rr_denoise_device(c, d, W, H, C, dev[0], dev[1], dev[2], dev[3], dev[4], base, nullptr);
     if (rc != RR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, base, bytes[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RR_OK;
+}
+
+// ---- temporal accumulation (render_temporal.inc, temporal_tap.hpp) ----
+// One kernel launch per call, no scratch.  It reads no scene and counts nothing: frame state and pending stats stay as
+// they are.
+static_assert(sizeof(rr_temporal_desc) == 32, "rr_temporal_desc is 32 bytes (rray.h)");
+static_assert(sizeof(rr_temporal_frame) == 48, "rr_temporal_frame is 48 bytes (rray.h)");
+
+static bool tp_cameras_equal(const rr_camera* a, const rr_camera* b) {
+    bool eq = a->hsize == b->hsize && a->vsize == b->vsize && a->field_of_view == b->field_of_view &&
+              a->pixel_size == b->pixel_size && a->half_width == b->half_width && a->half_height == b->half_height;
+    for (int i = 0; i < 16; ++i) eq = eq && a->transform[i] == b->transform[i];
+    return eq;
+}
+
+static rr::TpFrame tp_frame(const rr_temporal_frame* f) {
+    return rr::TpFrame{static_cast<const double*>(f->image),   static_cast<const double*>(f->depth),
+                       static_cast<const double*>(f->normal),  static_cast<const int32_t*>(f->object),
+                       static_cast<const int32_t*>(f->count),  static_cast<const double*>(f->m2)};
+}
+
+// what every temporal entry refuses of its arguments (the context apart); fills the kernel's arguments
+static int tp_check(const rr_temporal_desc* d, int64_t W, int64_t H, int32_t C, const rr_camera* cam,
+                    const rr_temporal_frame* cur, const rr_camera* prev_cam, const rr_temporal_frame* prev, const void* out,
+                    const void* n_out, const void* m2_out, rr::TpConst* K, rr::TpFrame* fc, rr::TpFrame* fp) {
+    if (!d || !cam || !prev_cam || !cur || !prev || !out || !n_out) return fail(RR_E_ARG, "rr_temporal: null argument");
+    if (C != 1 && C != 3) return fail(RR_E_ARG, "rr_temporal: channels must be 1 or 3");
+    if (W < 1 || H < 1) return fail(RR_E_ARG, "rr_temporal: width and height must be >= 1");
+    if (cam->hsize != W || cam->vsize != H || prev_cam->hsize != W || prev_cam->vsize != H)
+        return fail(RR_E_ARG, "rr_temporal: both cameras must have the frame's size");
+    if (!cur->image || !cur->depth || !prev->image || !prev->depth || !prev->count)
+        return fail(RR_E_ARG, "rr_temporal: the image and depth planes of both frames and the previous count plane are required");
+    if (d->flags & ~RR_TP_OBJECT) return fail(RR_E_ARG, "rr_temporal: unknown flag bits");
+    if (d->max_history < 1 || d->max_history > RR_MAX_TEMPORAL_HISTORY)
+        return fail(RR_E_ARG, "rr_temporal: max_history must be in 1.." + std::to_string(RR_MAX_TEMPORAL_HISTORY));
+    if (!(d->alpha >= 0.0 && d->alpha <= 1.0)) return fail(RR_E_ARG, "rr_temporal: alpha must be in 0..1");
+    for (double s : {d->sigma_plane, d->sigma_normal})
+        if (!(std::isfinite(s) && s >= 0.0)) return fail(RR_E_ARG, "rr_temporal: every sigma must be finite and >= 0");
+    int32_t t = 0;
+    if (d->flags & RR_TP_OBJECT) t |= rr::TP_T_OBJECT;
+    if (d->sigma_normal > 0.0) t |= rr::TP_T_NORMAL;
+    if (d->sigma_plane > 0.0) t |= rr::TP_T_PLANE;
+    if (((t & rr::TP_T_OBJECT) && (!cur->object || !prev->object)) || ((t & rr::TP_T_NORMAL) && (!cur->normal || !prev->normal)) ||
+        ((t & rr::TP_T_PLANE) && !cur->normal))
+        return fail(RR_E_ARG, "rr_temporal: a term that is switched on needs its planes");
+    if ((m2_out != nullptr) != (prev->m2 != nullptr))
+        return fail(RR_E_ARG, "rr_temporal: m2_out and the previous frame's m2 go together");
+    if (W > (((int64_t)1 << 31) - 1) / H) return fail(RR_E_LIMIT, "a temporal frame must hold fewer than 2^31 pixels");
+    const size_t n = (size_t)(W * H), img = n * (size_t)C * sizeof(double);
+    const void* outs[3] = {out, n_out, m2_out};
+    const size_t out_bytes[3] = {img, n * sizeof(int32_t), img};
+    const void* ins[10] = {cur->image, cur->depth, cur->normal, cur->object, prev->image,
+                           prev->depth, prev->normal, prev->object, prev->count, prev->m2};
+    const size_t in_bytes[10] = {img, n * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t), img,
+                                 n * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t), n * sizeof(int32_t), img};
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 10; ++b)
+            if (dn_overlap(outs[a], out_bytes[a], ins[b], in_bytes[b])) return fail(RR_E_ARG, "rr_temporal: an output overlaps an input");
+        for (int b = a + 1; b < 3; ++b)
+            if (dn_overlap(outs[a], out_bytes[a], outs[b], out_bytes[b])) return fail(RR_E_ARG, "rr_temporal: two outputs overlap");
+    }
+    double inv[16], pinv[16];
+    int rc = rr_camera_inverse(cam, inv);
+    if (rc != RR_OK) return rc;
+    rc = rr_camera_inverse(prev_cam, pinv);
+    if (rc != RR_OK) return rc;
+    K->cur = rr::tp_camera(inv, cam->half_width, cam->half_height, cam->pixel_size);
+    K->prev = rr::tp_camera(pinv, prev_cam->half_width, prev_cam->half_height, prev_cam->pixel_size);
+    for (int i = 0; i < 12; ++i) K->T[i] = prev_cam->transform[i];
+    K->alpha = d->alpha;
+    K->sigma_plane = d->sigma_plane;
+    K->sigma_normal = d->sigma_normal;
+    K->W = W;
+    K->H = H;
+    K->terms = t;
+    K->max_history = d->max_history;
+    K->is_static = tp_cameras_equal(cam, prev_cam) ? 1 : 0;
+    K->pad = 0;
+    *fc = tp_frame(cur);
+    *fp = tp_frame(prev);
+    fc->count = nullptr;  // previous frame only
+    fc->m2 = nullptr;
+    return RR_OK;
+}
+
+int rr_temporal_reference(const rr_temporal_desc* d, int64_t W, int64_t H, int32_t C, const rr_camera* cam,
+                          const rr_temporal_frame* cur, const rr_camera* prev_cam, const rr_temporal_frame* prev, double* out,
+                          int32_t* n_out, double* m2_out) {
+    rr::TpConst K{};
+    rr::TpFrame fc{}, fp{};
+    int rc = tp_check(d, W, H, C, cam, cur, prev_cam, prev, out, n_out, m2_out, &K, &fc, &fp);
+    if (rc != RR_OK) return rc;
+    double unused[3];
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t x = 0; x < W; ++x) {
+            const int64_t p = y * W + x;
+            if (C == 3 && m2_out)
+                rr::tp_pixel<3, true>(K, fc, fp, x, y, out + 3 * p, n_out + p, m2_out + 3 * p);
+            else if (C == 3)
+                rr::tp_pixel<3, false>(K, fc, fp, x, y, out + 3 * p, n_out + p, unused);
+            else if (m2_out)
+                rr::tp_pixel<1, true>(K, fc, fp, x, y, out + p, n_out + p, m2_out + p);
+            else
+                rr::tp_pixel<1, false>(K, fc, fp, x, y, out + p, n_out + p, unused);
+        }
+    return RR_OK;
+}
+
+static int tp_ctx_check(const rr_ctx* c) {
+    if (!c) return fail(RR_E_ARG, "null context");
+    if (c->group) return fail(RR_E_ARG, "rr_temporal needs a single-device context (no multi-device or virtual context)");
+    return RR_OK;
+}
+
+int rr_temporal_device(rr_ctx* c, const rr_temporal_desc* d, int64_t W, int64_t H, int32_t C, const rr_camera* cam,
+                       const rr_temporal_frame* cur, const rr_camera* prev_cam, const rr_temporal_frame* prev, void* d_out,
+                       void* d_n_out, void* d_m2_out, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = tp_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    rr::TpConst K{};
+    rr::TpFrame fc{}, fp{};
+    rc = tp_check(d, W, H, C, cam, cur, prev_cam, prev, d_out, d_n_out, d_m2_out, &K, &fc, &fp);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    HIPCHK(rr::launch_temporal(K, C, fc, fp, c->tp_rows != 0, static_cast<double*>(d_out), static_cast<int32_t*>(d_n_out),
+                               static_cast<double*>(d_m2_out), st));
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+int rr_temporal(rr_ctx* c, const rr_temporal_desc* d, int64_t W, int64_t H, int32_t C, const rr_camera* cam,
+                const rr_temporal_frame* cur, const rr_camera* prev_cam, const rr_temporal_frame* prev, double* out,
+                int32_t* n_out, double* m2_out) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = tp_ctx_check(c);
+    if (rc != RR_OK) return rc;
+    rr::TpConst K{};
+    rr::TpFrame fc{}, fp{};
+    rc = tp_check(d, W, H, C, cam, cur, prev_cam, prev, out, n_out, m2_out, &K, &fc, &fp);
+    if (rc != RR_OK) return rc;
+    const size_t n = (size_t)(W * H), img = n * C * sizeof(double);
+    // one device block: out, n_out, m2_out first, then the planes that are given, each 256-byte aligned
+    const void* host[13] = {out,         n_out,       m2_out,       cur->image,   cur->depth,  cur->normal, cur->object,
+                            prev->image, prev->depth, prev->normal, prev->object, prev->count, prev->m2};
+    const size_t bytes[13] = {img, n * sizeof(int32_t), img, img, n * sizeof(double), n * 3 * sizeof(double),
+                              n * sizeof(int32_t), img, n * sizeof(double), n * 3 * sizeof(double), n * sizeof(int32_t),
+                              n * sizeof(int32_t), img};
+    size_t off[13], total = 0;
+    for (int k = 0; k < 13; ++k) {
+        off[k] = total;
+        if (host[k]) total += (bytes[k] + 255) & ~(size_t)255;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_ctx(c));  // tp_host may grow, and a call on another stream may still read it
+    HIPCHK(c->tp_host.ensure(total));
+    char* base = c->tp_host.as<char>();
+    void* dev[13];
+    for (int k = 0; k < 13; ++k) {
+        dev[k] = host[k] ? base + off[k] : nullptr;
+        if (k >= 3 && host[k]) HIPCHK(hipMemcpyAsync(dev[k], host[k], bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    const rr_temporal_frame dc{dev[3], dev[4], dev[5], dev[6], nullptr, nullptr};
+    const rr_temporal_frame dp{dev[7], dev[8], dev[9], dev[10], dev[11], dev[12]};
+    rc = rr_temporal_device(c, d, W, H, C, cam, &dc, prev_cam, &dp, dev[0], dev[1], dev[2], nullptr);
+    if (rc != RR_OK) return rc;
+    for (int k = 0; k < 3; ++k)
+        if (host[k]) HIPCHK(hipMemcpyAsync(const_cast<void*>(host[k]), dev[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return RR_OK;
 }

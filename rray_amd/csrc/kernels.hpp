@@ -446,4 +446,14 @@ constexpr int RR_DN_LDS_MAX_STEP = 2;
 hipError_t launch_denoise_level(const DnLevel& L, bool lds, int32_t channels, int64_t W, int64_t H, const double* src,
                                 const DnGuide* guides, double* dst, hipStream_t stream);
 
+// Temporal accumulation (render_temporal.inc in render_rays.hip; the definition is rray.h's
+// RR_HAS_TEMPORAL block, its arithmetic temporal_tap.hpp's).
+struct TpConst;
+struct TpFrame;
+// temporal_kernel<channels, m2_out != null, tile width>: out, n_out and m2_out of every pixel of a K.W x K.H frame
+// (W * H < 2^31, channels 1 or 3; every plane a term of K.terms reads must be given).  rows: the row-major lane map
+// (a block is 256 x 1 pixels) instead of the 32 x 8 tile; the same result bit for bit.
+hipError_t launch_temporal(const TpConst& K, int32_t channels, const TpFrame& cur, const TpFrame& prev, bool rows,
+                           double* out, int32_t* n_out, double* m2_out, hipStream_t stream);
+
 }  // namespace rr

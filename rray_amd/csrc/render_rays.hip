@@ -12,6 +12,7 @@
 //   render_denoise.inc  the edge-avoiding denoiser's pack and level kernels (rr_denoise_device), by denoise_tap.hpp
 //   render_indirect.inc the one-bounce indirect rays, their live list and the resolve step (rr_indirect_at_device,
 //                       rr_render_indirect_device)
+//   render_temporal.inc temporal accumulation's one kernel (rr_temporal_device), by temporal_tap.hpp
 // None of the others reads the scene.  The queries' walks are the existing kernels' (hit_kernel's ray-batch instantiation, the
 // colour families with A.rays0, shadow_query_kernel), launched on the caller's buffers as they are.
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "denoise_tap.hpp"
 #include "device_core.inc"
 #include "kernels.hpp"
+#include "temporal_tap.hpp"
 #include "wavefront.hpp"
 
 namespace rr {
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(256) hit_records_ordered_kernel(const int32_t*
 #include "render_ao.inc"
 #include "render_indirect.inc"
 #include "render_denoise.inc"
+#include "render_temporal.inc"
 
 hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;

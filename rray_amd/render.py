@@ -706,6 +706,27 @@ class Renderer:
         p = [C.c_void_p(x) if x else None for x in (d_in, d_depth, d_normal, d_object, d_albedo, d_out, stream)]
         check(lib().rr_denoise_device(self.h, C.byref(d), width, height, channels, *p))
 
+    # ---- temporal accumulation (rray.h RR_HAS_TEMPORAL) ----
+    def temporal(self, img, tp, cam, prev_cam, depth, normal=None, object=None, prev=None, moments=False):
+        """rr_temporal: `img` (H, W), (H, W, 1) or (H, W, 3) f64 blended on the device with the history `prev` (what the
+        previous call returned; None: no history) seen from `prev_cam` -> dict(out, n, m2, depth, normal, object): the
+        accumulated image (img's shape), the int32 history lengths, the second moments (None unless `moments`) and this
+        frame's planes — a valid `prev` for the next call.  temporal_filter of the same arguments, bit for bit."""
+        return _temporal_call(lambda *a: lib().rr_temporal(self.h, *a), img, tp, cam, prev_cam, depth, normal, object, prev,
+                              moments)
+
+    def temporal_device(self, tp, width, height, channels, cam, prev_cam, cur, prev, d_out, d_n, d_m2=None, stream=None):
+        """rr_temporal_device: device buffers (ints: device pointers).  `cur` and `prev` are dicts of rr_temporal_frame's
+        fields (image, depth, normal, object, count, m2; a missing key or None: no plane); d_out height * width *
+        channels f64, d_n height * width int32, d_m2 like d_out or None.  Ordered on `stream` (int or None), not
+        synchronised; last_stats() is left as it is."""
+        d = tp.desc()
+        fc, fp = (_lib.TemporalFrame(*[f.get(k) or None for k in ("image", "depth", "normal", "object", "count", "m2")])
+                  for f in (cur, prev))
+        p = [C.c_void_p(x) if x else None for x in (d_out, d_n, d_m2, stream)]
+        check(lib().rr_temporal_device(self.h, C.byref(d), width, height, channels, C.byref(cam), C.byref(fc),
+                                       C.byref(prev_cam), C.byref(fp), *p))
+
 
 def _spread(q, bits, step):
     out = np.zeros(q.shape, np.uint32)
@@ -1118,6 +1139,205 @@ def denoise_filter(img, dn, depth=None, normal=None, object=None, albedo=None):
                     ws[P] = np.where(ok, ws[P] + w, ws[P])
             F = np.where(void[..., None], F, acc / np.where(void, 1.0, ws)[..., None])
     return F.reshape(np.shape(img))
+
+
+class Temporal:
+    """rr_temporal_desc (rray.h RR_HAS_TEMPORAL): the history length is capped at `max_history`; `alpha` is the floor of
+    the blend factor (0: a running mean); a sigma of 0 switches its term off; object=True skips taps on another object
+    id."""
+
+    def __init__(self, max_history=32, alpha=0.0, sigma_plane=0.01, sigma_normal=0.1, object=True):
+        self.max_history = int(max_history)
+        self.alpha, self.sigma_plane, self.sigma_normal = float(alpha), float(sigma_plane), float(sigma_normal)
+        self.object = bool(object)
+
+    def desc(self):
+        return _lib.TemporalDesc(_lib.RR_TP_OBJECT if self.object else 0, self.max_history, self.alpha, self.sigma_plane,
+                                 self.sigma_normal)
+
+    def __repr__(self):
+        return (f"Temporal(max_history={self.max_history}, alpha={self.alpha}, sigma_plane={self.sigma_plane}, "
+                f"sigma_normal={self.sigma_normal}, object={self.object})")
+
+
+def _temporal_args(img, depth, normal, object, prev, moments):
+    """The current frame and the history as contiguous arrays of rr_temporal's types -> (a, cur, hist, (H, W, C)).
+    prev=None is a history of zero counts over the current planes."""
+    if depth is None:
+        raise ValueError("temporal: the depth plane is required")
+    a, cur, (H, W, Cn) = _denoise_args(img, depth, normal, object, None)
+    if prev is None:
+        hist = {"out": np.zeros_like(a), "n": np.zeros((H, W), np.int32), "m2": np.zeros_like(a) if moments else None,
+                "depth": cur["depth"], "normal": cur["normal"], "object": cur["object"]}
+        return a, cur, hist, (H, W, Cn)
+    if prev.get("out") is None or prev.get("n") is None or prev.get("depth") is None:
+        raise ValueError("temporal: a history holds at least out, n and depth")
+    pa, planes, shape = _denoise_args(prev["out"], prev["depth"], prev.get("normal"), prev.get("object"), None)
+    if shape != (H, W, Cn):
+        raise ValueError(f"temporal: the history has shape {shape}, the image {(H, W, Cn)}")
+    n = np.ascontiguousarray(prev["n"], np.int32)
+    if n.shape != (H, W):
+        raise ValueError(f"temporal: the history's counts have shape {n.shape}, the image needs {(H, W)}")
+    m2 = None
+    if moments:
+        if prev.get("m2") is None:
+            raise ValueError("temporal: moments=True needs a history with m2")
+        m2 = np.ascontiguousarray(prev["m2"], np.float64).reshape(H, W, Cn)
+    return a, cur, {"out": pa, "n": n, "m2": m2, **planes}, (H, W, Cn)
+
+
+def _vp(a):
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _temporal_call(entry, img, tp, cam, prev_cam, depth, normal, object, prev, moments):
+    a, cur, hist, (H, W, Cn) = _temporal_args(img, depth, normal, object, prev, moments)
+    out, n = np.zeros_like(a), np.zeros((H, W), np.int32)
+    m2 = np.zeros_like(a) if moments else None
+    d = tp.desc()
+    fc = _lib.TemporalFrame(_vp(a), _vp(cur["depth"]), _vp(cur["normal"]), _vp(cur["object"]), None, None)
+    fp = _lib.TemporalFrame(_vp(hist["out"]), _vp(hist["depth"]), _vp(hist["normal"]), _vp(hist["object"]), _vp(hist["n"]),
+                            _vp(hist["m2"]))
+    check(entry(C.byref(d), W, H, Cn, C.byref(cam), C.byref(fc), C.byref(prev_cam), C.byref(fp), _vp(out), _vp(n), _vp(m2)))
+    shape = np.shape(img)
+    return {"out": out.reshape(shape), "n": n, "m2": None if m2 is None else m2.reshape(shape), "depth": cur["depth"],
+            "normal": cur["normal"], "object": cur["object"]}
+
+
+def temporal_reference(img, tp, cam, prev_cam, depth, normal=None, object=None, prev=None, moments=False):
+    """rr_temporal_reference: the C definition on the host (single thread, no device), by the function the kernel calls.
+    Renderer.temporal's arguments and result."""
+    return _temporal_call(lib().rr_temporal_reference, img, tp, cam, prev_cam, depth, normal, object, prev, moments)
+
+
+def temporal_variance(out, m2):
+    """The per-pixel variance estimate of an accumulated image and its second moments: maximum(m2 - out * out, 0)."""
+    out, m2 = np.asarray(out, np.float64), np.asarray(m2, np.float64)
+    return np.maximum(m2 - out * out, 0.0)
+
+
+def _camera_fields(cam):
+    return (cam.hsize, cam.vsize, cam.field_of_view, cam.pixel_size, cam.half_width, cam.half_height) + tuple(cam.transform)
+
+
+def temporal_filter(img, tp, cam, prev_cam, depth, normal=None, object=None, prev=None, moments=False,
+                    return_history=False):
+    """Temporal accumulation in numpy (rray.h RR_HAS_TEMPORAL), the kernel's definition and its tests' reference,
+    vectorised over the frame: Renderer.temporal's arguments and result.  Plain f64 in the header's order, with
+    M = camera_inverse(cam), M' = camera_inverse(prev_cam), T' = prev_cam.transform:
+      void(p): not z_p < inf, or object given and id_p < 0: out = in, n = 1, m2 = in in
+      P = o + z d of the pinhole ray through the pixel centre
+      static cameras (every field ==): the one tap q = p, w = 1, te = z
+      else c = T' P; no tap unless c_z < 0; fx = (half_width' - c_x / -c_z) / pixel_size' - 0.5, fy likewise; no tap
+      unless -1 < fx < W and -1 < fy < H; the four bilinear taps around (fx, fy), te = |P - o'|
+      a tap is skipped when it lies outside the frame, is void or has count < 1 in the history, lies on another object
+      (tp.object), has 1 - n_p.n_q > sigma_normal, lies further than sigma_plane te from p's tangent plane, or w is not > 0
+      h = sum w hist / sum w; n = min(min count + 1, max_history); a = max(1 / n, alpha); out = h + (in - h) a
+    return_history=True adds h (NaN where no tap survived), ws, fx and fy to the result."""
+    a, cur, hist, (H, W, Cn) = _temporal_args(img, depth, normal, object, prev, moments)
+    sig = (tp.sigma_plane, tp.sigma_normal)
+    if Cn not in (1, 3) or not 1 <= tp.max_history <= _lib.RR_MAX_TEMPORAL_HISTORY or not 0.0 <= tp.alpha <= 1.0 or \
+            not all(math.isfinite(x) and x >= 0.0 for x in sig):
+        raise ValueError("temporal_filter: 1 or 3 channels, max_history in 1..2^20, alpha in 0..1, sigmas finite and >= 0")
+    on_p, on_n = (x > 0.0 for x in sig)
+    if (tp.object and (cur["object"] is None or hist["object"] is None)) or (on_p and cur["normal"] is None) or \
+            (on_n and (cur["normal"] is None or hist["normal"] is None)):
+        raise ValueError("temporal_filter: a term that is switched on needs its planes")
+    if (cam.hsize, cam.vsize, prev_cam.hsize, prev_cam.vsize) != (W, H, W, H):
+        raise ValueError("temporal_filter: both cameras must have the frame's size")
+    M, Mp = camera_inverse(cam), camera_inverse(prev_cam)
+    T = np.array(list(prev_cam.transform), np.float64)
+
+    def X(m, x, y, z):
+        return [((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3] * 1.0 for r in range(3)]
+
+    def dirs(m, c, o, xs, ys):
+        wx = c.half_width - (xs.astype(np.float64) + 0.5) * c.pixel_size
+        wy = c.half_height - (ys.astype(np.float64) + 0.5) * c.pixel_size
+        f = X(m, wx, wy, -1.0)
+        d = [f[r] - o[r] for r in range(3)]
+        mag = np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+        return [d[r] / mag for r in range(3)]
+
+    with np.errstate(all="ignore"):
+        z, ids, nrm = cur["depth"], cur["object"], cur["normal"]
+        pz, pid, pn, pcnt, pimg, pm2 = hist["depth"], hist["object"], hist["normal"], hist["n"], hist["out"], hist["m2"]
+        void = ~(z < np.inf)
+        if ids is not None:
+            void |= ids < 0
+        pvoid = ~(pz < np.inf)
+        if pid is not None:
+            pvoid |= pid < 0
+        ys, xs = np.mgrid[0:H, 0:W]
+        o = [np.float64(v) for v in X(M, 0.0, 0.0, 0.0)]
+        op = [np.float64(v) for v in X(Mp, 0.0, 0.0, 0.0)]
+        d = dirs(M, cam, o, xs, ys)
+        P = [o[r] + z * d[r] for r in range(3)]
+        cand = ~void
+        if all(u == v for u, v in zip(_camera_fields(cam), _camera_fields(prev_cam))):  # a NaN is unequal to itself
+            taps = [(xs, ys, np.ones((H, W)))]
+            te = z
+            fx, fy = xs.astype(np.float64), ys.astype(np.float64)
+        else:
+            c = [((T[4 * r] * P[0] + T[4 * r + 1] * P[1]) + T[4 * r + 2] * P[2]) + T[4 * r + 3] * 1.0 for r in range(3)]
+            cand &= c[2] < 0.0
+            m = -c[2]
+            sx, sy = c[0] / m, c[1] / m
+            fx = (prev_cam.half_width - sx) / prev_cam.pixel_size - 0.5
+            fy = (prev_cam.half_height - sy) / prev_cam.pixel_size - 0.5
+            cand &= (fx > -1.0) & (fx < float(W)) & (fy > -1.0) & (fy < float(H))
+            fx0, fy0 = np.floor(fx), np.floor(fy)
+            ax, ay = fx - fx0, fy - fy0
+            x0 = np.where(cand, fx0, 0.0).astype(np.int64)
+            y0 = np.where(cand, fy0, 0.0).astype(np.int64)
+            taps = [(x0 + i, y0 + j, (ax if i else 1.0 - ax) * (ay if j else 1.0 - ay)) for j in (0, 1) for i in (0, 1)]
+            e = [P[r] - op[r] for r in range(3)]
+            te = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])
+        acc, accm2 = np.zeros((H, W, Cn)), np.zeros((H, W, Cn))
+        ws = np.zeros((H, W))
+        nmin = np.full((H, W), np.iinfo(np.int32).max, np.int64)
+        cnt = np.zeros((H, W), np.int64)
+        for qx, qy, w in taps:
+            ok = cand & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+            qx, qy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
+            ok &= ~pvoid[qy, qx]
+            nq = pcnt[qy, qx].astype(np.int64)
+            ok &= nq >= 1
+            if tp.object:
+                ok &= pid[qy, qx] == ids
+            if on_n:
+                nqv = pn[qy, qx]
+                dot = (nrm[..., 0] * nqv[..., 0] + nrm[..., 1] * nqv[..., 1]) + nrm[..., 2] * nqv[..., 2]
+                ok &= (1.0 - dot) <= tp.sigma_normal
+            if on_p:
+                dq = dirs(Mp, prev_cam, op, qx, qy)
+                zq = pz[qy, qx]
+                Q = [op[r] + zq * dq[r] for r in range(3)]
+                g = (nrm[..., 0] * (Q[0] - P[0]) + nrm[..., 1] * (Q[1] - P[1])) + nrm[..., 2] * (Q[2] - P[2])
+                ok &= np.abs(g) <= tp.sigma_plane * te
+            ok &= w > 0.0
+            acc = np.where(ok[..., None], acc + w[..., None] * pimg[qy, qx], acc)
+            if pm2 is not None:
+                accm2 = np.where(ok[..., None], accm2 + w[..., None] * pm2[qy, qx], accm2)
+            ws = np.where(ok, ws + w, ws)
+            nmin = np.where(ok, np.minimum(nmin, nq), nmin)
+            cnt += ok
+        keep = cnt > 0
+        n = np.where(keep, np.minimum(nmin + 1, tp.max_history), 1).astype(np.int32)
+        bl = 1.0 / n.astype(np.float64)
+        bl = np.where(bl < tp.alpha, tp.alpha, bl)[..., None]
+        h = acc / ws[..., None]
+        out = np.where(keep[..., None], h + (a - h) * bl, a)
+        m2 = None
+        if pm2 is not None:
+            hm2 = accm2 / ws[..., None]
+            m2 = np.where(keep[..., None], hm2 + (a * a - hm2) * bl, a * a)
+    shape = np.shape(img)
+    res = {"out": out.reshape(shape), "n": n, "m2": None if m2 is None else m2.reshape(shape), "depth": cur["depth"],
+           "normal": cur["normal"], "object": cur["object"]}
+    if return_history:
+        res.update(h=np.where(keep[..., None], h, np.nan), ws=ws, fx=fx, fy=fy)
+    return res
 
 
 def adaptive_mask(frame, threshold):
