@@ -791,6 +791,107 @@ int rr_temporal_device(rr_ctx* ctx, const rr_temporal_desc* desc, int64_t width,
                        const rr_camera* cam, const rr_temporal_frame* cur, const rr_camera* prev_cam,
                        const rr_temporal_frame* prev, void* d_out, void* d_n_out, void* d_m2_out, void* hip_stream);
 
+/* ---- variance-guided denoising: a per-pixel noise estimate steers the filter (additive to ABI 11; test
+ * RR_HAS_DENOISE_VAR) ----
+ * Two composable entries that join rr_temporal to an a-trous filter (spatiotemporal variance-guided filtering): rr_variance
+ * turns an image — with rr_temporal's moments where there is history, from a guided window where there is none — into a
+ * per-pixel variance plane, and rr_denoise_var is rr_denoise's filter with the colour tolerance of each pixel
+ * following that plane, which it carries through the levels.  The chain rr_render_*_device -> rr_temporal_device ->
+ * rr_variance_device -> rr_denoise_var_device leaves nothing on the host.
+ * Guides, their rounding to float, void(p) and the frames' layouts are rr_denoise's (the RR_HAS_DENOISE block above).
+ * All arithmetic is f64 in exactly the order written, no contraction; the only functions are fabs and the comparisons.
+ * Guide terms: for an off-centre tap q seen from p, the object (1), normal (3), depth (4) and albedo (5) terms of
+ *   rr_denoise in that order and with its arithmetic, r = (double)(max(|dx|, |dy|) * step), applied to the starting
+ *   weight w; a term whose t is not > 0.0 skips the tap.  The colour term is not among them.
+ *
+ * rr_variance: `in` (H x W x C doubles, C in {1, 3}), optional m2 (H x W x C) and count (int32 H x W) — rr_temporal's
+ * m2_out and n_out, both or neither — and the optional guide planes give var, H x W doubles.  For pixel p = (x, y):
+ *   if void(p): V = 0.0
+ *   else if count is given and count[p] >= min_history (the temporal branch):
+ *     v_c = m2[p][c] - in[p][c] * in[p][c]; if !(v_c > 0.0) then v_c = 0.0
+ *     V = ((v_0 + v_1) + v_2) / (double)count[p], or v_0 / (double)count[p] for C = 1.  Divided by the history length, V
+ *     is the variance of the accumulated mean: what the difference of two accumulated pixels is measured against.
+ *     Under rr_temporal's `alpha` floor the mean weighs recent frames more than 1 / count, so V under-estimates the
+ *     noise there.  (min_history = 0 with count[p] = 0 divides by zero as written.)
+ *   else (the spatial branch): s1[c] = s2[c] = 0.0, ws = 0.0; for dy = -3..3 (outer), dx = -3..3 (inner),
+ *     q = (x + dx, y + dy):
+ *       skip the tap if q lies outside the frame, or if void(q)
+ *       w = 1.0; if (dx, dy) != (0, 0), the guide terms with step 1; skip the tap unless w > 0.0
+ *       s1[c] = s1[c] + w * in[q][c]; s2[c] = s2[c] + w * (in[q][c] * in[q][c]); ws = ws + w
+ *     m_c = s1[c] / ws; v_c = s2[c] / ws - m_c * m_c; if !(v_c > 0.0) then v_c = 0.0
+ *     V = (v_0 + v_1) + v_2, or v_0 for C = 1, not divided
+ * (rray_amd.variance_estimate is the same in numpy.)
+ *
+ * rr_denoise_var: `in` (H x W x C), var (H x W doubles, required: rr_variance's output or the caller's own estimate)
+ * and the guide planes give `out` and, when var_out is not NULL, var_out (H x W): the variance of the filtered image.
+ * sigma_color is NOT halved per level: sc2 = sigma_color * sigma_color at every level, and the shrinking variance does
+ * the narrowing.  F_0 = in, V_0 = var.  For level i = 0..I-1, s = 2^i, and pixel p = (x, y):
+ *   if void(p): F_{i+1}[p] = F_i[p], V_{i+1}[p] = V_i[p]
+ *   else the prefiltered variance: ga = gs = 0.0; for ey = -1..1 (outer), ex = -1..1 (inner), q = (x + ex, y + ey)
+ *     (step 1 at every level): skip q outside the frame or void; gw = g[ey+1] * g[ex+1] with g = (1/4, 1/2, 1/4);
+ *     ga = ga + gw * V_i[q]; gs = gs + gw
+ *     gv = ga / gs; den = sc2 * gv + epsilon (two roundings)
+ *     acc[c] = 0.0, va = 0.0, ws = 0.0; for dy = -2..2 (outer), dx = -2..2 (inner), q = (x + dx * s, y + dy * s):
+ *       skip the tap if q lies outside the frame, or if void(q)
+ *       w = h[dy+2] * h[dx+2], h as in rr_denoise
+ *       if (dx, dy) != (0, 0): the guide terms with step s; then, if sigma_color > 0: dc as in rr_denoise's colour
+ *         term; t = 1.0 + dc / den; skip the tap unless t > 0.0; w = w * (1.0 / (t * t))
+ *       skip the tap unless w > 0.0
+ *       acc[c] = acc[c] + w * F_i[q][c]; va = va + (w * w) * V_i[q]; ws = ws + w
+ *     F_{i+1}[p][c] = acc[c] / ws; V_{i+1}[p] = va / (ws * ws).  The centre tap always contributes, so ws > 0.
+ *   Where V is 0, den is epsilon, t * t may overflow and the tap then drops out by `w > 0.0`: a noise-free pixel keeps
+ *   its value.  The outputs are F_I and V_I.
+ * (rray_amd.denoise_var_filter is the same in numpy.)
+ *
+ * Refusals, rr_denoise's: RR_E_ARG for a null ctx, desc, in or out (var for rr_variance); C not 1 or 3; W or H < 1;
+ * iterations outside 1..RR_MAX_DENOISE_ITERATIONS; a sigma that is negative or not finite; unknown flag bits; a term
+ * that is switched on without its plane; an output overlapping an input or another output; a multi-device or virtual
+ * context.  RR_E_LIMIT: W * H >= 2^31.  In addition RR_E_ARG: m2 without count or count without m2; min_history outside
+ * 0..RR_MAX_TEMPORAL_HISTORY; an epsilon that is not finite or not > 0; a null var for rr_denoise_var.  No scene is
+ * needed.
+ * The _reference entries: host only, no context: the definition, by the very functions the kernels call.
+ * rr_variance, rr_denoise_var: host buffers, run on the device, blocking.
+ * rr_variance_device, rr_denoise_var_device: device buffers on the context's device, enqueued on `hip_stream` (NULL: ctx
+ *   stream) and NOT synchronised; the stream claim and device guard of the other _device entries.  One pack kernel per
+ *   call, then one variance kernel, or one level kernel per iteration through rr_denoise_device's two scratch images
+ *   and two context-owned variance planes that grow on demand (none for iterations == 1).  Frame state and
+ *   rr_last_stats are left alone, as by rr_denoise_device. */
+#define RR_HAS_DENOISE_VAR 1
+typedef struct {
+    int32_t flags;       /* RR_DN_OBJECT or 0; other bits: RR_E_ARG */
+    int32_t min_history; /* 0..RR_MAX_TEMPORAL_HISTORY: a pixel with count >= min_history takes the temporal branch */
+    double sigma_normal; /* the spatial branch's guide terms: each sigma finite and >= 0; 0 switches the term off */
+    double sigma_depth;
+    double sigma_albedo;
+} rr_variance_desc; /* 32 bytes */
+typedef struct {
+    int32_t iterations; /* the fields of rr_denoise_desc, with its meanings and ranges */
+    int32_t flags;
+    double sigma_color; /* in standard deviations of the pixel's noise: t = 1 + dc / (sigma_color^2 * gv + epsilon) */
+    double sigma_normal;
+    double sigma_depth;
+    double sigma_albedo;
+    double epsilon; /* finite and > 0: the colour tolerance (squared) of a pixel whose variance is 0 */
+} rr_denoise_var_desc; /* 48 bytes */
+int rr_variance_reference(const rr_variance_desc* desc, int64_t width, int64_t height, int32_t channels, const double* in,
+                          const double* m2, const int32_t* count, const double* depth, const double* normal,
+                          const int32_t* object, const double* albedo, double* var);
+int rr_variance(rr_ctx* ctx, const rr_variance_desc* desc, int64_t width, int64_t height, int32_t channels,
+                const double* in, const double* m2, const int32_t* count, const double* depth, const double* normal,
+                const int32_t* object, const double* albedo, double* var);
+int rr_variance_device(rr_ctx* ctx, const rr_variance_desc* desc, int64_t width, int64_t height, int32_t channels,
+                       const void* d_in, const void* d_m2, const void* d_count, const void* d_depth, const void* d_normal,
+                       const void* d_object, const void* d_albedo, void* d_var, void* hip_stream);
+int rr_denoise_var_reference(const rr_denoise_var_desc* desc, int64_t width, int64_t height, int32_t channels,
+                             const double* in, const double* var, const double* depth, const double* normal,
+                             const int32_t* object, const double* albedo, double* out, double* var_out);
+int rr_denoise_var(rr_ctx* ctx, const rr_denoise_var_desc* desc, int64_t width, int64_t height, int32_t channels,
+                   const double* in, const double* var, const double* depth, const double* normal, const int32_t* object,
+                   const double* albedo, double* out, double* var_out);
+int rr_denoise_var_device(rr_ctx* ctx, const rr_denoise_var_desc* desc, int64_t width, int64_t height, int32_t channels,
+                          const void* d_in, const void* d_var, const void* d_depth, const void* d_normal,
+                          const void* d_object, const void* d_albedo, void* d_out, void* d_var_out, void* hip_stream);
+
 /* Host-only inspection of the flattening (no device needed): per-object inverse transforms as the
  * kernels use them (4x4, row 3 == 0,0,0,1), group bounding boxes (group.rs:128-149; zeros for
  * non-groups) and each object's index in the flattened depth-first order (-1: not in the tree).

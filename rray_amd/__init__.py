@@ -25,6 +25,12 @@ from .render import (  # noqa: F401
     temporal_reference,
     temporal_filter,
     temporal_variance,
+    Variance,
+    variance_reference,
+    variance_estimate,
+    DenoiseVar,
+    denoise_var_reference,
+    denoise_var_filter,
     Indirect,
     indirect_rays,
     indirect_resolve,
@@ -45,5 +51,5 @@ from .render import (  # noqa: F401
 )
 
 __all__ = ["Renderer", "SceneBuilder", "YamlScene", "camera", "part_rows", "quantize", "write_png",
-           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "ray_order_keys", "Lens", "lens_rays", "lens_resolve", "Ao", "ao_directions", "ao_targets", "ao_resolve", "Denoise", "denoise_reference", "denoise_filter", "Temporal", "temporal_reference", "temporal_filter", "temporal_variance", "Indirect", "indirect_rays", "indirect_resolve", "indirect_compose", "object_diffuse", "RRError",
+           "render_scene_from_str", "render_scene_from_file", "device_count", "rccl_unique_id", "stage_row_offset", "unshuffle", "balance_bands", "adaptive_mask", "ray_order_keys", "Lens", "lens_rays", "lens_resolve", "Ao", "ao_directions", "ao_targets", "ao_resolve", "Denoise", "denoise_reference", "denoise_filter", "Temporal", "temporal_reference", "temporal_filter", "temporal_variance", "Variance", "variance_reference", "variance_estimate", "DenoiseVar", "denoise_var_reference", "denoise_var_filter", "Indirect", "indirect_rays", "indirect_resolve", "indirect_compose", "object_diffuse", "RRError",
            "lib"]

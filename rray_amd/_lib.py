@@ -86,7 +86,9 @@ EXPORTS = ["rr_abi_version", "rr_last_error", "rr_device_count", "rr_create", "r
            "rr_hit_at_device_ordered", "rr_camera_inverse", "rr_lens_rays_device", "rr_render_lens",
            "rr_render_lens_device", "rr_ao_directions", "rr_ao_at_device", "rr_render_ao", "rr_render_ao_device",
            "rr_denoise_reference", "rr_denoise", "rr_denoise_device", "rr_indirect_at_device", "rr_render_indirect",
-           "rr_render_indirect_device", "rr_temporal_reference", "rr_temporal", "rr_temporal_device"]
+           "rr_render_indirect_device", "rr_temporal_reference", "rr_temporal", "rr_temporal_device",
+           "rr_variance_reference", "rr_variance", "rr_variance_device", "rr_denoise_var_reference", "rr_denoise_var",
+           "rr_denoise_var_device"]
 RCCL_ID_BYTES = 128
 
 # ABI 11: first-hit queries and AOV frames
@@ -151,6 +153,18 @@ class TemporalFrame(C.Structure):
     """rr_temporal_frame (RR_HAS_TEMPORAL): one frame's planes, host or device pointers by entry."""
     _fields_ = [("image", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("object", C.c_void_p),
                 ("count", C.c_void_p), ("m2", C.c_void_p)]
+
+
+class VarianceDesc(C.Structure):
+    """rr_variance_desc (RR_HAS_DENOISE_VAR): flags, the history a pixel needs for the temporal branch, and the three
+    guide sigmas of the spatial branch (0 switches a term off)."""
+    _fields_ = [("flags", C.c_int32), ("min_history", C.c_int32), ("sigma_normal", C.c_double),
+                ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
+
+
+class DenoiseVarDesc(C.Structure):
+    """rr_denoise_var_desc (RR_HAS_DENOISE_VAR): rr_denoise_desc's fields and epsilon."""
+    _fields_ = DenoiseDesc._fields_ + [("epsilon", C.c_double)]
 
 
 def hit_dtype():
@@ -275,6 +289,16 @@ def lib():
     L.rr_temporal_reference.argtypes = _tp + [C.c_void_p] * 3
     L.rr_temporal.argtypes = [C.c_void_p] + _tp + [C.c_void_p] * 3
     L.rr_temporal_device.argtypes = [C.c_void_p] + _tp + [C.c_void_p] * 4
+    # variance-guided denoising (RR_HAS_DENOISE_VAR)
+    _vr = [C.POINTER(VarianceDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _I, _D, _D, _I, _D, _D]
+    L.rr_variance_reference.argtypes = _vr
+    L.rr_variance.argtypes = [C.c_void_p] + _vr
+    L.rr_variance_device.argtypes = [C.c_void_p, C.POINTER(VarianceDesc), C.c_int64, C.c_int64, C.c_int32] + [C.c_void_p] * 9
+    _dv = [C.POINTER(DenoiseVarDesc), C.c_int64, C.c_int64, C.c_int32, _D, _D, _D, _D, _I, _D, _D, _D]
+    L.rr_denoise_var_reference.argtypes = _dv
+    L.rr_denoise_var.argtypes = [C.c_void_p] + _dv
+    L.rr_denoise_var_device.argtypes = ([C.c_void_p, C.POINTER(DenoiseVarDesc), C.c_int64, C.c_int64, C.c_int32] +
+                                        [C.c_void_p] * 9)
     # one-bounce indirect light (RR_HAS_INDIRECT)
     L.rr_indirect_at_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(IndirectDesc),
                                         C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]

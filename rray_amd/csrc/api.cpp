@@ -18,6 +18,7 @@
 #include "flatten.hpp"
 #include "ao_dir.hpp"
 #include "denoise_tap.hpp"
+#include "denoise_var_tap.hpp"
 #include "temporal_tap.hpp"
 #include "frame_plan.hpp"
 #include "kernels.hpp"
@@ -110,6 +111,9 @@ struct rr_ctx {
     // between (8 * channels bytes per pixel each; none for one iteration), grown on demand; dn_host: the device copies
     // of rr_denoise's host buffers
     DBuf dn_guides, dn_img[2], dn_host;
+    // variance-guided denoising (rr_denoise_var_device): the two variance planes the levels ping-pong between beside
+    // dn_img (8 bytes per pixel each; none for one iteration), grown on demand.  rr_variance_device needs dn_guides only
+    DBuf dv_var[2];
     // levels with holes of at most this many pixels run the LDS-tiled kernel, the wider ones the direct kernel.  -1: the
     // measured choice (DESIGN.md §3.22's A/B): 2 for one channel, 1 for three.  RRAY_DENOISE_LDS=<0..2> overrides (0: every
     // level direct), read at context creation
@@ -956,7 +960,7 @@ void rr_destroy(rr_ctx* c) {
                     &c->tile_cost, &c->tile_perm, &c->tile_hist, &c->deep, &c->deep_count, &c->node_object, &c->hitrec, &c->aov,
                     &c->adapt_flags, &c->adapt_blocks, &c->adapt_counts, &c->adapt_list, &c->adapt_mask, &c->views,
                     &c->shadow_sink, &c->order_scratch, &c->order_perm, &c->lens_rays, &c->lens_rgb,
-                    &c->ao_count, &c->ao_rays, &c->ind_rays, &c->ind_rgb, &c->ind_cam, &c->ind_list, &c->ind_counts, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host,
+                    &c->ao_count, &c->ao_rays, &c->ind_rays, &c->ind_rgb, &c->ind_cam, &c->ind_list, &c->ind_counts, &c->dn_guides, &c->dn_img[0], &c->dn_img[1], &c->dn_host, &c->dv_var[0], &c->dv_var[1],
                     &c->tp_host})
         b->release();
     for (auto& b : c->comb) b.release();
@@ -2559,15 +2563,16 @@ bool dn_overlap(const void* a, size_t na, const void* b, size_t nb) {
 }  // namespace
 
 // what every denoiser entry refuses of its arguments (the context apart); fills the terms that are switched on
-static int dn_check(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const DnPlanes& P, int32_t* terms) {
-    if (!d || !P.in || !P.out) return fail(RR_E_ARG, "rr_denoise: null argument");
-    if (C != 1 && C != 3) return fail(RR_E_ARG, "rr_denoise: channels must be 1 or 3");
-    if (W < 1 || H < 1) return fail(RR_E_ARG, "rr_denoise: width and height must be >= 1");
+static int dn_check(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, const DnPlanes& P, int32_t* terms,
+                    const std::string& who = "rr_denoise") {
+    if (!d || !P.in || !P.out) return fail(RR_E_ARG, who + ": null argument");
+    if (C != 1 && C != 3) return fail(RR_E_ARG, who + ": channels must be 1 or 3");
+    if (W < 1 || H < 1) return fail(RR_E_ARG, who + ": width and height must be >= 1");
     if (d->iterations < 1 || d->iterations > RR_MAX_DENOISE_ITERATIONS)
-        return fail(RR_E_ARG, "rr_denoise: iterations must be in 1.." + std::to_string(RR_MAX_DENOISE_ITERATIONS));
-    if (d->flags & ~RR_DN_OBJECT) return fail(RR_E_ARG, "rr_denoise: unknown flag bits");
+        return fail(RR_E_ARG, who + ": iterations must be in 1.." + std::to_string(RR_MAX_DENOISE_ITERATIONS));
+    if (d->flags & ~RR_DN_OBJECT) return fail(RR_E_ARG, who + ": unknown flag bits");
     for (double s : {d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo})
-        if (!(std::isfinite(s) && s >= 0.0)) return fail(RR_E_ARG, "rr_denoise: every sigma must be finite and >= 0");
+        if (!(std::isfinite(s) && s >= 0.0)) return fail(RR_E_ARG, who + ": every sigma must be finite and >= 0");
     int32_t t = 0;
     if (d->flags & RR_DN_OBJECT) t |= rr::DN_T_OBJECT;
     if (d->sigma_color > 0.0) t |= rr::DN_T_COLOR;
@@ -2576,13 +2581,13 @@ static int dn_check(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t C, c
     if (d->sigma_albedo > 0.0) t |= rr::DN_T_ALBEDO;
     if (((t & rr::DN_T_OBJECT) && !P.object) || ((t & rr::DN_T_NORMAL) && !P.normal) ||
         ((t & rr::DN_T_DEPTH) && !P.depth) || ((t & rr::DN_T_ALBEDO) && !P.albedo))
-        return fail(RR_E_ARG, "rr_denoise: a term that is switched on needs its plane");
+        return fail(RR_E_ARG, who + ": a term that is switched on needs its plane");
     if (W > (((int64_t)1 << 31) - 1) / H) return fail(RR_E_LIMIT, "a denoised frame must hold fewer than 2^31 pixels");
     const size_t n = (size_t)(W * H), img = n * (size_t)C * sizeof(double);
     if (dn_overlap(P.out, img, P.in, img) || dn_overlap(P.out, img, P.depth, n * sizeof(double)) ||
         dn_overlap(P.out, img, P.normal, n * 3 * sizeof(double)) || dn_overlap(P.out, img, P.object, n * sizeof(int32_t)) ||
         dn_overlap(P.out, img, P.albedo, n * 3 * sizeof(double)))
-        return fail(RR_E_ARG, "rr_denoise: out overlaps an input");
+        return fail(RR_E_ARG, who + ": out overlaps an input");
     *terms = t;
     return RR_OK;
 }
@@ -2619,9 +2624,9 @@ int rr_denoise_reference(const rr_denoise_desc* d, int64_t W, int64_t H, int32_t
     return RR_OK;
 }
 
-static int dn_ctx_check(const rr_ctx* c) {
+static int dn_ctx_check(const rr_ctx* c, const std::string& who = "rr_denoise") {
     if (!c) return fail(RR_E_ARG, "null context");
-    if (c->group) return fail(RR_E_ARG, "rr_denoise needs a single-device context (no multi-device or virtual context)");
+    if (c->group) return fail(RR_E_ARG, who + " needs a single-device context (no multi-device or virtual context)");
     return RR_OK;
 }
 
@@ -2692,6 +2697,258 @@ int rr_denoise(rr_ctx* c, const rr_denoise_desc* d, int64_t W, int64_t H, int32_
     rc = rr_denoise_device(c, d, W, H, C, dev[0], dev[1], dev[2], dev[3], dev[4], base, nullptr);
     if (rc != RR_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, base, bytes[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RR_OK;
+}
+
+// ---- variance-guided denoising (render_denoise_var.inc, denoise_var_tap.hpp) ----
+// rr_variance: one pack kernel and one variance kernel.  rr_denoise_var: one pack kernel and one level kernel per
+// iteration, the images through dn_img[2] as in rr_denoise and the variance planes through dv_var[2].  Neither reads a
+// scene or counts anything: frame state and pending stats stay as they are.
+static_assert(sizeof(rr_variance_desc) == 32, "rr_variance_desc is 32 bytes (rray.h)");
+static_assert(sizeof(rr_denoise_var_desc) == 48, "rr_denoise_var_desc is 48 bytes (rray.h)");
+
+namespace {
+struct VarPlanes {
+    const void *in, *m2, *count, *depth, *normal, *object, *albedo;
+    void* var;
+};
+}  // namespace
+
+// what every rr_variance entry refuses of its arguments (the context apart); fills the guide terms that are switched on
+static int var_check(const rr_variance_desc* d, int64_t W, int64_t H, int32_t C, const VarPlanes& P, int32_t* terms) {
+    if (!d || !P.in || !P.var) return fail(RR_E_ARG, "rr_variance: null argument");
+    if (C != 1 && C != 3) return fail(RR_E_ARG, "rr_variance: channels must be 1 or 3");
+    if (W < 1 || H < 1) return fail(RR_E_ARG, "rr_variance: width and height must be >= 1");
+    if (d->flags & ~RR_DN_OBJECT) return fail(RR_E_ARG, "rr_variance: unknown flag bits");
+    if (d->min_history < 0 || d->min_history > RR_MAX_TEMPORAL_HISTORY)
+        return fail(RR_E_ARG, "rr_variance: min_history must be in 0.." + std::to_string(RR_MAX_TEMPORAL_HISTORY));
+    for (double s : {d->sigma_normal, d->sigma_depth, d->sigma_albedo})
+        if (!(std::isfinite(s) && s >= 0.0)) return fail(RR_E_ARG, "rr_variance: every sigma must be finite and >= 0");
+    if ((P.m2 != nullptr) != (P.count != nullptr)) return fail(RR_E_ARG, "rr_variance: m2 and count go together");
+    int32_t t = 0;
+    if (d->flags & RR_DN_OBJECT) t |= rr::DN_T_OBJECT;
+    if (d->sigma_normal > 0.0) t |= rr::DN_T_NORMAL;
+    if (d->sigma_depth > 0.0) t |= rr::DN_T_DEPTH;
+    if (d->sigma_albedo > 0.0) t |= rr::DN_T_ALBEDO;
+    if (((t & rr::DN_T_OBJECT) && !P.object) || ((t & rr::DN_T_NORMAL) && !P.normal) ||
+        ((t & rr::DN_T_DEPTH) && !P.depth) || ((t & rr::DN_T_ALBEDO) && !P.albedo))
+        return fail(RR_E_ARG, "rr_variance: a term that is switched on needs its plane");
+    if (W > (((int64_t)1 << 31) - 1) / H) return fail(RR_E_LIMIT, "a variance plane must hold fewer than 2^31 pixels");
+    const size_t n = (size_t)(W * H), img = n * (size_t)C * sizeof(double), vb = n * sizeof(double);
+    if (dn_overlap(P.var, vb, P.in, img) || dn_overlap(P.var, vb, P.m2, img) || dn_overlap(P.var, vb, P.count, n * sizeof(int32_t)) ||
+        dn_overlap(P.var, vb, P.depth, n * sizeof(double)) || dn_overlap(P.var, vb, P.normal, n * 3 * sizeof(double)) ||
+        dn_overlap(P.var, vb, P.object, n * sizeof(int32_t)) || dn_overlap(P.var, vb, P.albedo, n * 3 * sizeof(double)))
+        return fail(RR_E_ARG, "rr_variance: var overlaps an input");
+    *terms = t;
+    return RR_OK;
+}
+
+int rr_variance_reference(const rr_variance_desc* d, int64_t W, int64_t H, int32_t C, const double* in, const double* m2,
+                          const int32_t* count, const double* depth, const double* normal, const int32_t* object,
+                          const double* albedo, double* var) {
+    int32_t terms = 0;
+    int rc = var_check(d, W, H, C, VarPlanes{in, m2, count, depth, normal, object, albedo, var}, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    std::vector<rr::DnGuide> g((size_t)n);
+    for (int64_t p = 0; p < n; ++p) g[(size_t)p] = rr::dn_guide(p, depth, normal, object, albedo);
+    const rr::DnLevel G = rr::dv_guide_level(terms, 1, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t x = 0; x < W; ++x)
+            var[y * W + x] = C == 3 ? rr::dv_variance<3>(G, d->min_history, W, H, x, y, in, g.data(), m2, count)
+                                    : rr::dv_variance<1>(G, d->min_history, W, H, x, y, in, g.data(), m2, count);
+    return RR_OK;
+}
+
+int rr_variance_device(rr_ctx* c, const rr_variance_desc* d, int64_t W, int64_t H, int32_t C, const void* d_in,
+                       const void* d_m2, const void* d_count, const void* d_depth, const void* d_normal,
+                       const void* d_object, const void* d_albedo, void* d_var, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c, "rr_variance");
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rc = var_check(d, W, H, C, VarPlanes{d_in, d_m2, d_count, d_depth, d_normal, d_object, d_albedo, d_var}, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the scratch is claimed before it may grow: a call on another stream may still read the buffers that ensure frees
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    if (c->dn_guides.bytes < (size_t)n * sizeof(rr::DnGuide))
+        HIPCHK(hipStreamSynchronize(st));  // growing frees: nothing enqueued may still use the old buffer
+    HIPCHK(c->dn_guides.ensure((size_t)n * sizeof(rr::DnGuide)));
+    rr::DnGuide* g = c->dn_guides.as<rr::DnGuide>();
+    HIPCHK(rr::launch_denoise_pack(n, static_cast<const double*>(d_depth), static_cast<const double*>(d_normal),
+                                   static_cast<const int32_t*>(d_object), static_cast<const double*>(d_albedo), g, st));
+    const rr::DnLevel G = rr::dv_guide_level(terms, 1, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+    HIPCHK(rr::launch_variance(G, d->min_history, C, W, H, static_cast<const double*>(d_in), static_cast<const double*>(d_m2),
+                               static_cast<const int32_t*>(d_count), g, static_cast<double*>(d_var), st));
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+// The blocking entries' device block in dn_host: the outputs first, then the inputs that are given, each 256-byte
+// aligned.  Copies the inputs on the context's stream; dev[k] is null where host[k] is.
+static int dv_stage(rr_ctx* c, int n_planes, int n_out, void* const* host, const size_t* bytes, void** dev) {
+    size_t off[16], total = 0;
+    for (int k = 0; k < n_planes; ++k) {
+        off[k] = total;
+        if (host[k]) total += (bytes[k] + 255) & ~(size_t)255;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(sync_ctx(c));  // dn_host may grow, and a call on another stream may still read it
+    HIPCHK(c->dn_host.ensure(total));
+    char* base = c->dn_host.as<char>();
+    for (int k = 0; k < n_planes; ++k) {
+        dev[k] = host[k] ? base + off[k] : nullptr;
+        if (k >= n_out && host[k]) HIPCHK(hipMemcpyAsync(dev[k], host[k], bytes[k], hipMemcpyHostToDevice, c->stream));
+    }
+    return RR_OK;
+}
+
+int rr_variance(rr_ctx* c, const rr_variance_desc* d, int64_t W, int64_t H, int32_t C, const double* in, const double* m2,
+                const int32_t* count, const double* depth, const double* normal, const int32_t* object, const double* albedo,
+                double* var) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c, "rr_variance");
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rc = var_check(d, W, H, C, VarPlanes{in, m2, count, depth, normal, object, albedo, var}, &terms);
+    if (rc != RR_OK) return rc;
+    const size_t n = (size_t)(W * H), img = n * C * sizeof(double);
+    void* host[8] = {var, (void*)in, (void*)m2, (void*)count, (void*)depth, (void*)normal, (void*)object, (void*)albedo};
+    const size_t bytes[8] = {n * sizeof(double), img, img, n * sizeof(int32_t), n * sizeof(double), n * 3 * sizeof(double),
+                             n * sizeof(int32_t), n * 3 * sizeof(double)};
+    void* dev[8];
+    rc = dv_stage(c, 8, 1, host, bytes, dev);
+    if (rc != RR_OK) return rc;
+    rc = rr_variance_device(c, d, W, H, C, dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[0], nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(var, dev[0], bytes[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return RR_OK;
+}
+
+// what every rr_denoise_var entry refuses of its arguments (the context apart): rr_denoise's refusals, then its own
+static int dv_check(const rr_denoise_var_desc* d, int64_t W, int64_t H, int32_t C, const DnPlanes& P, const void* var,
+                    const void* var_out, rr_denoise_desc* base, int32_t* terms) {
+    if (!d) return fail(RR_E_ARG, "rr_denoise_var: null argument");
+    *base = rr_denoise_desc{d->iterations, d->flags, d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo};
+    int rc = dn_check(base, W, H, C, P, terms, "rr_denoise_var");
+    if (rc != RR_OK) return rc;
+    if (!var) return fail(RR_E_ARG, "rr_denoise_var: null var");
+    if (!(std::isfinite(d->epsilon) && d->epsilon > 0.0)) return fail(RR_E_ARG, "rr_denoise_var: epsilon must be finite and > 0");
+    const size_t n = (size_t)(W * H), img = n * (size_t)C * sizeof(double), vb = n * sizeof(double);
+    if (dn_overlap(P.out, img, var, vb)) return fail(RR_E_ARG, "rr_denoise_var: out overlaps an input");
+    if (dn_overlap(var_out, vb, P.in, img) || dn_overlap(var_out, vb, var, vb) || dn_overlap(var_out, vb, P.depth, n * sizeof(double)) ||
+        dn_overlap(var_out, vb, P.normal, n * 3 * sizeof(double)) || dn_overlap(var_out, vb, P.object, n * sizeof(int32_t)) ||
+        dn_overlap(var_out, vb, P.albedo, n * 3 * sizeof(double)))
+        return fail(RR_E_ARG, "rr_denoise_var: var_out overlaps an input");
+    if (dn_overlap(var_out, vb, P.out, img)) return fail(RR_E_ARG, "rr_denoise_var: the two outputs overlap");
+    return RR_OK;
+}
+
+int rr_denoise_var_reference(const rr_denoise_var_desc* d, int64_t W, int64_t H, int32_t C, const double* in,
+                             const double* var, const double* depth, const double* normal, const int32_t* object,
+                             const double* albedo, double* out, double* var_out) {
+    int32_t terms = 0;
+    rr_denoise_desc base;
+    int rc = dv_check(d, W, H, C, DnPlanes{in, depth, normal, object, albedo, out}, var, var_out, &base, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    std::vector<rr::DnGuide> g((size_t)n);
+    for (int64_t p = 0; p < n; ++p) g[(size_t)p] = rr::dn_guide(p, depth, normal, object, albedo);
+    std::vector<double> f[2], v[2], vlast;
+    for (int k = 0; k < 2; ++k)
+        if (d->iterations > k + 1) f[k].resize((size_t)n * C), v[k].resize((size_t)n);
+    if (!var_out) vlast.resize((size_t)n);
+    const double *src = in, *vsrc = var;
+    for (int32_t i = 0; i < d->iterations; ++i) {
+        const bool last = i == d->iterations - 1;
+        double* dst = last ? out : f[i & 1].data();
+        double* vdst = last ? (var_out ? var_out : vlast.data()) : v[i & 1].data();
+        const rr::DnLevel L = rr::dv_level(terms, i, d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+        for (int64_t y = 0; y < H; ++y)
+            for (int64_t x = 0; x < W; ++x) {
+                const int64_t p = y * W + x;
+                if (C == 3)
+                    rr::dv_pixel<3>(L, d->epsilon, W, H, x, y, src, vsrc, g.data(), dst + 3 * p, vdst + p);
+                else
+                    rr::dv_pixel<1>(L, d->epsilon, W, H, x, y, src, vsrc, g.data(), dst + p, vdst + p);
+            }
+        src = dst;
+        vsrc = vdst;
+    }
+    return RR_OK;
+}
+
+int rr_denoise_var_device(rr_ctx* c, const rr_denoise_var_desc* d, int64_t W, int64_t H, int32_t C, const void* d_in,
+                          const void* d_var, const void* d_depth, const void* d_normal, const void* d_object,
+                          const void* d_albedo, void* d_out, void* d_var_out, void* hip_stream) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c, "rr_denoise_var");
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rr_denoise_desc base;
+    rc = dv_check(d, W, H, C, DnPlanes{d_in, d_depth, d_normal, d_object, d_albedo, d_out}, d_var, d_var_out, &base, &terms);
+    if (rc != RR_OK) return rc;
+    const int64_t n = W * H;
+    const size_t img = (size_t)n * (size_t)C * sizeof(double), vb = (size_t)n * sizeof(double);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // the scratch is claimed before it may grow: a call on another stream may still read the buffers that ensure frees
+    HIPCHK(claim_stream(c, st));
+    StreamClaim claim{c, st};
+    const int32_t I = d->iterations;
+    if (c->dn_guides.bytes < (size_t)n * sizeof(rr::DnGuide) || (I > 1 && (c->dn_img[0].bytes < img || c->dv_var[0].bytes < vb)) ||
+        (I > 2 && (c->dn_img[1].bytes < img || c->dv_var[1].bytes < vb)))
+        HIPCHK(hipStreamSynchronize(st));  // growing frees: nothing enqueued may still use the old buffers
+    HIPCHK(c->dn_guides.ensure((size_t)n * sizeof(rr::DnGuide)));
+    for (int k = 0; k < 2; ++k)
+        if (I > k + 1) {
+            HIPCHK(c->dn_img[k].ensure(img));
+            HIPCHK(c->dv_var[k].ensure(vb));
+        }
+    rr::DnGuide* g = c->dn_guides.as<rr::DnGuide>();
+    HIPCHK(rr::launch_denoise_pack(n, static_cast<const double*>(d_depth), static_cast<const double*>(d_normal),
+                                   static_cast<const int32_t*>(d_object), static_cast<const double*>(d_albedo), g, st));
+    const double *src = static_cast<const double*>(d_in), *vsrc = static_cast<const double*>(d_var);
+    for (int32_t i = 0; i < I; ++i) {
+        const bool last = i == I - 1;
+        double* dst = last ? static_cast<double*>(d_out) : c->dn_img[i & 1].as<double>();
+        double* vdst = last ? static_cast<double*>(d_var_out) : c->dv_var[i & 1].as<double>();  // null: not stored
+        const rr::DnLevel L = rr::dv_level(terms, i, d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo);
+        HIPCHK(rr::launch_denoise_var_level(L, d->epsilon, C, W, H, src, vsrc, g, dst, vdst, st));
+        src = dst;
+        vsrc = vdst;
+    }
+    HIPCHK(claim.release());
+    return RR_OK;
+}
+
+int rr_denoise_var(rr_ctx* c, const rr_denoise_var_desc* d, int64_t W, int64_t H, int32_t C, const double* in,
+                   const double* var, const double* depth, const double* normal, const int32_t* object, const double* albedo,
+                   double* out, double* var_out) {
+    rr::DeviceGuard device_guard;  // the caller's current device is restored on return
+    int rc = dn_ctx_check(c, "rr_denoise_var");
+    if (rc != RR_OK) return rc;
+    int32_t terms = 0;
+    rr_denoise_desc base;
+    rc = dv_check(d, W, H, C, DnPlanes{in, depth, normal, object, albedo, out}, var, var_out, &base, &terms);
+    if (rc != RR_OK) return rc;
+    const size_t n = (size_t)(W * H), img = n * C * sizeof(double);
+    void* host[8] = {out, var_out, (void*)in, (void*)var, (void*)depth, (void*)normal, (void*)object, (void*)albedo};
+    const size_t bytes[8] = {img, n * sizeof(double), img, n * sizeof(double), n * sizeof(double), n * 3 * sizeof(double),
+                             n * sizeof(int32_t), n * 3 * sizeof(double)};
+    void* dev[8];
+    rc = dv_stage(c, 8, 2, host, bytes, dev);
+    if (rc != RR_OK) return rc;
+    rc = rr_denoise_var_device(c, d, W, H, C, dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[0], dev[1], nullptr);
+    if (rc != RR_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dev[0], bytes[0], hipMemcpyDeviceToHost, c->stream));
+    if (var_out) HIPCHK(hipMemcpyAsync(var_out, dev[1], bytes[1], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return RR_OK;
 }

@@ -446,6 +446,18 @@ constexpr int RR_DN_LDS_MAX_STEP = 2;
 hipError_t launch_denoise_level(const DnLevel& L, bool lds, int32_t channels, int64_t W, int64_t H, const double* src,
                                 const DnGuide* guides, double* dst, hipStream_t stream);
 
+// Variance-guided denoising (render_denoise_var.inc in render_rays.hip; the definition is rray.h's
+// RR_HAS_DENOISE_VAR block, its arithmetic denoise_var_tap.hpp's).  Both read the records of launch_denoise_pack.
+// variance_kernel<channels>: var[p] = dv_variance of every pixel of `in` (W x H x channels doubles, channels 1 or 3,
+// W * H < 2^31).  G: dv_guide_level(terms, 1, ...); m2 and count: rr_temporal's planes, both or neither.
+hipError_t launch_variance(const DnLevel& G, int32_t min_history, int32_t channels, int64_t W, int64_t H, const double* in,
+                           const double* m2, const int32_t* count, const DnGuide* guides, double* var, hipStream_t stream);
+// denoise_var_level_kernel<channels>: dst and vdst = one level of the filter over src and vsrc (src != dst, vsrc !=
+// vdst; vdst may be null: the level's variance is not stored).  L: dv_level(...).
+hipError_t launch_denoise_var_level(const DnLevel& L, double epsilon, int32_t channels, int64_t W, int64_t H,
+                                    const double* src, const double* vsrc, const DnGuide* guides, double* dst, double* vdst,
+                                    hipStream_t stream);
+
 // Temporal accumulation (render_temporal.inc in render_rays.hip; the definition is rray.h's
 // RR_HAS_TEMPORAL block, its arithmetic temporal_tap.hpp's).
 struct TpConst;

@@ -13,6 +13,8 @@
 //   render_indirect.inc the one-bounce indirect rays, their live list and the resolve step (rr_indirect_at_device,
 //                       rr_render_indirect_device)
 //   render_temporal.inc temporal accumulation's one kernel (rr_temporal_device), by temporal_tap.hpp
+//   render_denoise_var.inc  the per-pixel noise estimate and the variance-guided levels (rr_variance_device,
+//                       rr_denoise_var_device), by denoise_var_tap.hpp
 // None of the others reads the scene.  The queries' walks are the existing kernels' (hit_kernel's ray-batch instantiation, the
 // colour families with A.rays0, shadow_query_kernel), launched on the caller's buffers as they are.
 #include <algorithm>
@@ -20,6 +22,7 @@
 
 #include "ao_dir.hpp"
 #include "denoise_tap.hpp"
+#include "denoise_var_tap.hpp"
 #include "device_core.inc"
 #include "kernels.hpp"
 #include "temporal_tap.hpp"
@@ -125,6 +128,7 @@ __global__ void __launch_bounds__(256) hit_records_ordered_kernel(const int32_t*
 #include "render_ao.inc"
 #include "render_indirect.inc"
 #include "render_denoise.inc"
+#include "render_denoise_var.inc"
 #include "render_temporal.inc"
 
 hipError_t launch_camera_rays(const DevCamera& cam, bool affine, int64_t n, double* out, hipStream_t st) {

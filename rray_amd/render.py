@@ -727,6 +727,49 @@ class Renderer:
         check(lib().rr_temporal_device(self.h, C.byref(d), width, height, channels, C.byref(cam), C.byref(fc),
                                        C.byref(prev_cam), C.byref(fp), *p))
 
+    # ---- variance-guided denoising (rray.h RR_HAS_DENOISE_VAR) ----
+    def variance(self, img, vr, m2=None, count=None, depth=None, normal=None, object=None, albedo=None):
+        """rr_variance: the per-pixel noise estimate of `img` ((H, W), (H, W, 1) or (H, W, 3) f64) on the device, from
+        temporal()'s m2 and n where they are given and a pixel has vr.min_history frames, from a guided window
+        otherwise -> the (H, W) plane; variance_estimate of the same arguments, bit for bit."""
+        a, m2, count, planes, (H, W, Cn) = _variance_args(img, m2, count, depth, normal, object, albedo)
+        var = np.zeros((H, W), np.float64)
+        d = vr.desc()
+        check(lib().rr_variance(self.h, C.byref(d), W, H, Cn, _dp(a), None if m2 is None else _dp(m2),
+                                None if count is None else _ip(count), *_denoise_ptrs(planes), _dp(var)))
+        return var
+
+    def variance_device(self, vr, width, height, channels, d_in, d_var, d_m2=None, d_count=None, d_depth=None,
+                        d_normal=None, d_object=None, d_albedo=None, stream=None):
+        """rr_variance_device: device buffers (ints: device pointers; d_var height * width f64), ordered on `stream`
+        (int or None), not synchronised; last_stats() is left as it is."""
+        d = vr.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_in, d_m2, d_count, d_depth, d_normal, d_object, d_albedo, d_var, stream)]
+        check(lib().rr_variance_device(self.h, C.byref(d), width, height, channels, *p))
+
+    def denoise_var(self, img, var, dv, depth=None, normal=None, object=None, albedo=None, return_var=False):
+        """rr_denoise_var: `img` filtered on the device under the (H, W) variance plane `var` (variance()'s result or
+        the caller's own) -> an array of img's shape, or (image, variance plane of the filtered image) with return_var;
+        denoise_var_filter of the same arguments, bit for bit."""
+        a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+        v = _var_plane(var, H, W)
+        out = np.zeros_like(a)
+        vout = np.zeros((H, W), np.float64) if return_var else None
+        d = dv.desc()
+        check(lib().rr_denoise_var(self.h, C.byref(d), W, H, Cn, _dp(a), _dp(v), *_denoise_ptrs(planes), _dp(out),
+                                   None if vout is None else _dp(vout)))
+        out = out.reshape(np.shape(img))
+        return (out, vout) if return_var else out
+
+    def denoise_var_device(self, dv, width, height, channels, d_in, d_var, d_out, d_var_out=None, d_depth=None,
+                           d_normal=None, d_object=None, d_albedo=None, stream=None):
+        """rr_denoise_var_device: device buffers (ints: device pointers; d_in and d_out height * width * channels f64,
+        d_var and d_var_out height * width f64, d_var_out may be None), ordered on `stream` (int or None), not
+        synchronised; last_stats() is left as it is."""
+        d = dv.desc()
+        p = [C.c_void_p(x) if x else None for x in (d_in, d_var, d_depth, d_normal, d_object, d_albedo, d_out, d_var_out, stream)]
+        check(lib().rr_denoise_var_device(self.h, C.byref(d), width, height, channels, *p))
+
 
 def _spread(q, bits, step):
     out = np.zeros(q.shape, np.uint32)
@@ -1139,6 +1182,259 @@ def denoise_filter(img, dn, depth=None, normal=None, object=None, albedo=None):
                     ws[P] = np.where(ok, ws[P] + w, ws[P])
             F = np.where(void[..., None], F, acc / np.where(void, 1.0, ws)[..., None])
     return F.reshape(np.shape(img))
+
+
+class Variance:
+    """rr_variance_desc (rray.h RR_HAS_DENOISE_VAR): a pixel whose history holds at least `min_history` frames takes
+    its variance from rr_temporal's moments, the others from a guided 7 x 7 window of the image; a sigma of 0 switches
+    its guide term off; object=True skips taps on another object id."""
+
+    def __init__(self, min_history=4, sigma_normal=0.25, sigma_depth=0.05, sigma_albedo=0.0, object=False):
+        self.min_history = int(min_history)
+        self.sigma_normal, self.sigma_depth, self.sigma_albedo = float(sigma_normal), float(sigma_depth), float(sigma_albedo)
+        self.object = bool(object)
+
+    def desc(self):
+        return _lib.VarianceDesc(_lib.RR_DN_OBJECT if self.object else 0, self.min_history, self.sigma_normal,
+                                 self.sigma_depth, self.sigma_albedo)
+
+    def __repr__(self):
+        return (f"Variance(min_history={self.min_history}, sigma_normal={self.sigma_normal}, sigma_depth={self.sigma_depth}, "
+                f"sigma_albedo={self.sigma_albedo}, object={self.object})")
+
+
+class DenoiseVar:
+    """rr_denoise_var_desc (rray.h RR_HAS_DENOISE_VAR): Denoise's fields, with `sigma_color` in standard deviations of
+    each pixel's own noise (not halved per level), and `epsilon`, the squared colour tolerance of a noise-free pixel."""
+
+    def __init__(self, iterations, sigma_color=4.0, epsilon=1e-12, sigma_normal=0.25, sigma_depth=0.05, sigma_albedo=0.1,
+                 object=False):
+        self.iterations = int(iterations)
+        self.sigma_color, self.epsilon = float(sigma_color), float(epsilon)
+        self.sigma_normal, self.sigma_depth, self.sigma_albedo = float(sigma_normal), float(sigma_depth), float(sigma_albedo)
+        self.object = bool(object)
+
+    def desc(self):
+        return _lib.DenoiseVarDesc(self.iterations, _lib.RR_DN_OBJECT if self.object else 0, self.sigma_color,
+                                   self.sigma_normal, self.sigma_depth, self.sigma_albedo, self.epsilon)
+
+    def __repr__(self):
+        return (f"DenoiseVar(iterations={self.iterations}, sigma_color={self.sigma_color}, epsilon={self.epsilon}, "
+                f"sigma_normal={self.sigma_normal}, sigma_depth={self.sigma_depth}, sigma_albedo={self.sigma_albedo}, "
+                f"object={self.object})")
+
+
+def _variance_args(img, m2, count, depth, normal, object, albedo):
+    """_denoise_args and the moments and counts as contiguous arrays of rr_variance's types (None stays None)."""
+    a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+    if (m2 is None) != (count is None):
+        raise ValueError("variance: m2 and count go together")
+    if m2 is not None:
+        m2 = np.ascontiguousarray(m2, np.float64).reshape(H, W, Cn)
+        count = np.ascontiguousarray(count, np.int32)
+        if count.shape != (H, W):
+            raise ValueError(f"variance: the counts have shape {count.shape}, the image needs {(H, W)}")
+    return a, m2, count, planes, (H, W, Cn)
+
+
+def _var_plane(var, H, W):
+    v = np.ascontiguousarray(var, np.float64)
+    if v.shape != (H, W):
+        raise ValueError(f"denoise_var: the variance plane has shape {v.shape}, the image needs {(H, W)}")
+    return v
+
+
+def variance_reference(img, vr, m2=None, count=None, depth=None, normal=None, object=None, albedo=None):
+    """rr_variance_reference: the C definition on the host (single thread, no device), by the function the kernel calls
+    -> the (H, W) variance plane."""
+    a, m2, count, planes, (H, W, Cn) = _variance_args(img, m2, count, depth, normal, object, albedo)
+    var = np.zeros((H, W), np.float64)
+    d = vr.desc()
+    check(lib().rr_variance_reference(C.byref(d), W, H, Cn, _dp(a), None if m2 is None else _dp(m2),
+                                      None if count is None else _ip(count), *_denoise_ptrs(planes), _dp(var)))
+    return var
+
+
+def denoise_var_reference(img, var, dv, depth=None, normal=None, object=None, albedo=None, return_var=False):
+    """rr_denoise_var_reference: the C definition on the host -> the filtered image, or (image, (H, W) variance of the
+    filtered image) with return_var."""
+    a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+    v = _var_plane(var, H, W)
+    out = np.zeros_like(a)
+    vout = np.zeros((H, W), np.float64) if return_var else None
+    d = dv.desc()
+    check(lib().rr_denoise_var_reference(C.byref(d), W, H, Cn, _dp(a), _dp(v), *_denoise_ptrs(planes), _dp(out),
+                                         None if vout is None else _dp(vout)))
+    out = out.reshape(np.shape(img))
+    return (out, vout) if return_var else out
+
+
+def _dv_guides(planes, H, W):
+    """The guides as the definition reads them (rounded to f32 and widened) and the void mask."""
+    f32 = lambda v: None if v is None else v.astype(np.float32).astype(np.float64)  # noqa: E731
+    z, nrm, alb, ids = f32(planes["depth"]), f32(planes["normal"]), f32(planes["albedo"]), planes["object"]
+    void = np.zeros((H, W), bool)
+    if z is not None:
+        void |= ~(z < np.inf)
+    if ids is not None:
+        void |= ids < 0
+    return z, nrm, alb, ids, void
+
+
+def _dv_guide_terms(ok, w, P, Q, reach, g, on_o, sigma_normal, sigma_depth, sigma_albedo):
+    """The guide terms of rr_denoise (object, normal, depth, albedo, in this order) of the taps Q seen from the pixels
+    P, applied to the weights w -> (ok, w): a term whose t is not > 0 clears ok."""
+    z, nrm, alb, ids, _ = g
+    if on_o:
+        ok = ok & (ids[Q] == ids[P])
+    if sigma_normal > 0.0:
+        np_, nq = nrm[P], nrm[Q]
+        dot = (np_[..., 0] * nq[..., 0] + np_[..., 1] * nq[..., 1]) + np_[..., 2] * nq[..., 2]
+        e = 1.0 - dot
+        e = np.where(e < 0.0, 0.0, e)
+        t = 1.0 - e / sigma_normal
+        ok = ok & (t > 0.0)
+        w = w * (t * t)
+    if sigma_depth > 0.0:
+        t = 1.0 - np.abs(z[P] - z[Q]) / ((sigma_depth * np.abs(z[P])) * float(reach))
+        ok = ok & (t > 0.0)
+        w = w * (t * t)
+    if sigma_albedo > 0.0:
+        sa2 = np.float64(sigma_albedo) * np.float64(sigma_albedo)
+        da_ = alb[P] - alb[Q]
+        da = (da_[..., 0] * da_[..., 0] + da_[..., 1] * da_[..., 1]) + da_[..., 2] * da_[..., 2]
+        t = 1.0 - da / sa2
+        ok = ok & (t > 0.0)
+        w = w * (t * t)
+    return ok, w
+
+
+def _dv_check_terms(who, obj, sigmas, planes):
+    if not all(math.isfinite(x) and x >= 0.0 for x in sigmas):
+        raise ValueError(f"{who}: every sigma is finite and >= 0")
+    sn, sz, sa = sigmas[-3:]
+    if (obj and planes["object"] is None) or (sn > 0.0 and planes["normal"] is None) or \
+            (sz > 0.0 and planes["depth"] is None) or (sa > 0.0 and planes["albedo"] is None):
+        raise ValueError(f"{who}: a term that is switched on needs its plane")
+
+
+def _shifted(H, W, ox, oy):
+    """(P, Q): the pixels whose tap at offset (ox, oy) lies inside the frame, and the taps"""
+    return ((slice(max(0, -oy), H - max(0, oy)), slice(max(0, -ox), W - max(0, ox))),
+            (slice(max(0, oy), H - max(0, -oy)), slice(max(0, ox), W - max(0, -ox))))
+
+
+def _channel_sum(v):
+    return (v[..., 0] + v[..., 1]) + v[..., 2] if v.shape[-1] == 3 else v[..., 0]
+
+
+def variance_estimate(img, vr, m2=None, count=None, depth=None, normal=None, object=None, albedo=None):
+    """The per-pixel noise estimate in numpy (rray.h RR_HAS_DENOISE_VAR), the kernel's definition and its tests'
+    reference, vectorised over the frame with shifted slices -> the (H, W) plane.  Plain f64 in the header's order:
+      void(p): V = 0
+      count given and count[p] >= min_history: v_c = max(m2 - in in, 0) (a NaN gives 0); V = sum_c v_c / count[p]
+      otherwise, over dy = -3..3 (outer), dx = -3..3 (inner), q = p + (dx, dy) inside the frame and not void: w = 1,
+      off-centre taps take denoise_filter's object, normal, depth and albedo terms with step 1; taps with w > 0 add
+      w in[q] to s1, w (in[q] in[q]) to s2 and w to ws; m = s1 / ws, v_c = max(s2 / ws - m m, 0); V = sum_c v_c."""
+    a, m2, count, planes, (H, W, Cn) = _variance_args(img, m2, count, depth, normal, object, albedo)
+    if Cn not in (1, 3) or W < 1 or H < 1 or not 0 <= vr.min_history <= _lib.RR_MAX_TEMPORAL_HISTORY:
+        raise ValueError("variance_estimate: 1 or 3 channels, a frame of at least one pixel, min_history in 0..2^20")
+    sig = (vr.sigma_normal, vr.sigma_depth, vr.sigma_albedo)
+    _dv_check_terms("variance_estimate", vr.object, sig, planes)
+    with np.errstate(all="ignore"):
+        g = _dv_guides(planes, H, W)
+        void = g[4]
+        s1, s2, ws = np.zeros((H, W, Cn)), np.zeros((H, W, Cn)), np.zeros((H, W))
+        for dy in range(-3, 4):
+            for dx in range(-3, 4):
+                if abs(dx) >= W or abs(dy) >= H:
+                    continue
+                P, Q = _shifted(H, W, dx, dy)
+                ok = ~void[P] & ~void[Q]
+                w = np.ones(ok.shape)
+                if dx or dy:
+                    ok, w = _dv_guide_terms(ok, w, P, Q, max(abs(dx), abs(dy)), g, vr.object, *sig)
+                ok = ok & (w > 0.0)
+                Fq = a[Q]
+                # a tap that is skipped adds nothing (the sums are kept, not increased by 0.0)
+                s1[P] = np.where(ok[..., None], s1[P] + w[..., None] * Fq, s1[P])
+                s2[P] = np.where(ok[..., None], s2[P] + w[..., None] * (Fq * Fq), s2[P])
+                ws[P] = np.where(ok, ws[P] + w, ws[P])
+        m = s1 / ws[..., None]
+        v = s2 / ws[..., None] - m * m
+        V = _channel_sum(np.where(v > 0.0, v, 0.0))
+        if count is not None:
+            vt = m2 - a * a
+            Vt = _channel_sum(np.where(vt > 0.0, vt, 0.0)) / count.astype(np.float64)
+            V = np.where(count >= vr.min_history, Vt, V)
+        return np.where(void, 0.0, V)
+
+
+def denoise_var_filter(img, var, dv, depth=None, normal=None, object=None, albedo=None, return_var=False):
+    """The variance-guided filter in numpy (rray.h RR_HAS_DENOISE_VAR), the kernel's definition and its tests'
+    reference, vectorised over the frame: 9 + 25 shifted slices per level -> the filtered image, or (image, variance
+    plane of the filtered image) with return_var.  denoise_filter's levels with two differences.  The colour term of an
+    off-centre tap, applied after the guide terms, is t = 1 + dc / den, w *= 1 / (t t) with den = (sigma_color
+    sigma_color) gv + epsilon, sigma_color not halved per level and gv the 3 x 3 binomial (1/4, 1/2, 1/4) of the
+    level's variance plane around p over the pixels that are inside the frame and not void.  And the variance is
+    carried along: V' = sum (w w) V[q] / (ws ws) beside F' = sum w F[q] / ws; a void pixel keeps both."""
+    a, planes, (H, W, Cn) = _denoise_args(img, depth, normal, object, albedo)
+    V = _var_plane(var, H, W)
+    I = int(dv.iterations)
+    if not 1 <= I <= _lib.RR_MAX_DENOISE_ITERATIONS or Cn not in (1, 3) or W < 1 or H < 1:
+        raise ValueError("denoise_var_filter: iterations in 1..8, 1 or 3 channels, a frame of at least one pixel")
+    if not (math.isfinite(dv.epsilon) and dv.epsilon > 0.0):
+        raise ValueError("denoise_var_filter: epsilon is finite and > 0")
+    sig = (dv.sigma_normal, dv.sigma_depth, dv.sigma_albedo)
+    _dv_check_terms("denoise_var_filter", dv.object, (dv.sigma_color,) + sig, planes)
+    with np.errstate(all="ignore"):
+        g = _dv_guides(planes, H, W)
+        void = g[4]
+        h = (1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0)
+        b = (1.0 / 4.0, 1.0 / 2.0, 1.0 / 4.0)
+        sc2 = np.float64(dv.sigma_color) * np.float64(dv.sigma_color)
+        F = a
+        for i in range(I):
+            s = 1 << i
+            ga, gs = np.zeros((H, W)), np.zeros((H, W))
+            for ey in range(-1, 2):
+                for ex in range(-1, 2):
+                    if abs(ex) >= W or abs(ey) >= H:
+                        continue
+                    P, Q = _shifted(H, W, ex, ey)
+                    ok = ~void[P] & ~void[Q]
+                    gw = b[ey + 1] * b[ex + 1]
+                    ga[P] = np.where(ok, ga[P] + gw * V[Q], ga[P])
+                    gs[P] = np.where(ok, gs[P] + gw, gs[P])
+            den = sc2 * (ga / gs) + dv.epsilon
+            acc, va, ws = np.zeros((H, W, Cn)), np.zeros((H, W)), np.zeros((H, W))
+            for dy in range(-2, 3):
+                for dx in range(-2, 3):
+                    ox, oy = dx * s, dy * s
+                    if abs(ox) >= W or abs(oy) >= H:
+                        continue
+                    P, Q = _shifted(H, W, ox, oy)
+                    ok = ~void[P] & ~void[Q]
+                    w = np.full(ok.shape, h[dy + 2] * h[dx + 2])
+                    Fq = F[Q]
+                    if dx or dy:
+                        ok, w = _dv_guide_terms(ok, w, P, Q, max(abs(dx), abs(dy)) * s, g, dv.object, *sig)
+                        if dv.sigma_color > 0.0:
+                            d = F[P] - Fq
+                            dc = d[..., 0] * d[..., 0]
+                            if Cn == 3:
+                                dc = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                            t = 1.0 + dc / den[P]
+                            ok = ok & (t > 0.0)
+                            w = w * (1.0 / (t * t))
+                    ok = ok & (w > 0.0)
+                    acc[P] = np.where(ok[..., None], acc[P] + w[..., None] * Fq, acc[P])
+                    va[P] = np.where(ok, va[P] + (w * w) * V[Q], va[P])
+                    ws[P] = np.where(ok, ws[P] + w, ws[P])
+            F = np.where(void[..., None], F, acc / ws[..., None])
+            V = np.where(void, V, va / (ws * ws))
+    F = F.reshape(np.shape(img))
+    return (F, V) if return_var else F
 
 
 class Temporal:
