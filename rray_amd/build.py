@@ -80,7 +80,8 @@ VIEWS_HIT_UNITS = _variants("views_", "hit")  # rr_render_views_aov
 RAYS_UNITS = ["render_rays.hip"]
 SOURCES = (LEVEL_UNITS + PERSIST_UNITS + CHAIN_UNITS + TREE_UNITS + LISTED_UNITS + VIEWS_UNITS + HIT_UNITS + VIEWS_HIT_UNITS +
            ["render.hip", "render_adapt.hip", "render_views.hip"] + RAYS_UNITS +
-           ["api.cpp", "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp", "imgfmt.cpp"])
+           ["api.cpp", "api_queries.cpp", "api_frames.cpp", "api_sampled.cpp", "api_filters.cpp",  # the C ABI (api_ctx.hpp)
+            "multi.cpp", "flatten.cpp", "frontend.cpp", "yaml.cpp", "png.cpp", "jpeg.cpp", "imgfmt.cpp"])
 
 
 def source_digest():

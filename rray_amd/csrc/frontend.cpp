@@ -13,12 +13,11 @@
 
 #include "../../include/rray/rray.h"
 #include "png.hpp"
+#include "rr_error.hpp"
 #include "rr_math.hpp"
 #include "yaml.hpp"
 
 using rr::yaml::Node;
-
-void rr_set_error(const char* msg);  // api.cpp
 
 struct rr_scene {
     // registry (object/db.rs) in creation order; ids index every array

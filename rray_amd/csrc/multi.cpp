@@ -37,9 +37,8 @@
 #include "device_guard.hpp"
 #include "kernels.hpp"
 #include "partition.hpp"
+#include "rr_error.hpp"
 #include "trace.hpp"
-
-void rr_set_error(const char* msg);  // api.cpp
 
 namespace {
 

@@ -1,6 +1,6 @@
 // ao_pass_check.cpp — prints what rray_amd/csrc/frame_plan.hpp decides for the passes of rr_render_ao_device
 // (plan_ao_passes), the cases of tests/test_ao_host.py: one line per case, "ao <case> key=value ...".  The passes are
-// walked the way api.cpp walks them (first += points, the last pass takes what is left): sum is their total in points,
+// walked the way api_sampled.cpp walks them (first += points, the last pass takes what is left): sum is their total in points,
 // largest and smallest the extremes, count how many there were, misaligned how many start at a point index that is not
 // a multiple of 64, pass_pairs the largest pass's pairs.
 // It also runs rray_amd/csrc/ao_dir.hpp on the host over the basis's edge normals ("dir <case> finite=.. ..."), so the

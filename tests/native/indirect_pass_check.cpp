@@ -1,6 +1,6 @@
 // indirect_pass_check.cpp — prints what rray_amd/csrc/frame_plan.hpp decides for the passes of rr_indirect_at_device
 // and rr_render_indirect_device (plan_indirect_passes), the cases of tests/test_indirect_host.py: one line per case,
-// "ind <case> key=value ...".  The passes are walked the way api.cpp walks them (first += points, the last pass takes
+// "ind <case> key=value ...".  The passes are walked the way api_sampled.cpp walks them (first += points, the last pass takes
 // what is left): sum is their total in points, largest and smallest the extremes, count how many there were, misaligned
 // how many start at a point index or a ray index that is not a multiple of 64, pass_rays the largest pass's rays.
 // A stand-alone subject for -fsanitize=address,undefined on the header.

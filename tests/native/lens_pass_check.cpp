@@ -1,6 +1,6 @@
 // lens_pass_check.cpp — prints what rray_amd/csrc/frame_plan.hpp decides for the passes of rr_render_lens_device
 // (plan_lens_passes), the cases of tests/test_lens_host.py: one line per case, "lens <case> key=value ...".  The passes
-// are walked the way api.cpp walks them (first += pixels, the last pass takes what is left): sum is their total in
+// are walked the way api_sampled.cpp walks them (first += pixels, the last pass takes what is left): sum is their total in
 // pixels, largest and smallest the extremes, count how many there were, misaligned how many start at a ray index that
 // is not a multiple of 64.
 #include <algorithm>

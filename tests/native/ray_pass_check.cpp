@@ -1,6 +1,6 @@
 // ray_pass_check.cpp — prints what rray_amd/csrc/frame_plan.hpp decides for the passes of rr_hit_at_device
 // (plan_ray_passes), the cases of tests/test_rays_host.py: one line per case, "pass <case> key=value ...".  The pass
-// sizes are walked the way api.cpp walks them (first += pass, the last pass takes what is left): sum is their total,
+// sizes are walked the way api_queries.cpp walks them (first += pass, the last pass takes what is left): sum is their total,
 // largest and smallest the extremes, count how many there were.
 #include <algorithm>
 #include <cstdio>
